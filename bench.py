@@ -5,7 +5,14 @@ set (interaction, dt, update, cell sort).  Inputs are resident in HBM when the
 timed region starts.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4]
-                    [--dp DP] [--no-cpu-baseline]
+                    [--dp DP] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is
+given and prints the result line.  --full adds everything else: the pair counts and the
+roofline of the dominant kernel, the per-phase breakdown (a second, untimed run), the
+cfg3 timing beside cfg2, the developed-flow timing and the CPU baseline.
+--dump-outputs DIR writes the particle state after the last timed step (idp, pos, vel,
+rhop, code in idp order) as DIR/<name>.npy (DIR/<name>_rank<r>.npy for N>1).
 
 Workloads:
   cfg2 (default): 3D dam break, WCSPH + artificial viscosity + DDT2, Verlet.  N=1: the
@@ -243,11 +250,39 @@ def weak_dp(target_np: int) -> float:
     return float("%.6g" % lo)
 
 
+DUMP_MAX_BYTES = 60 << 20  # all of a rank's dumped arrays together (limit: 64 MB)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname: str, p: dict, rank: int, world: int) -> None:
+    """Writes the downloaded particle state `p` as <dirname>/<name>.npy, in idp order (the
+    solver's cell-sorted order is an internal detail; idp order compares build to build).
+    pos stays float64, idp becomes float64 (exact), the rest float32.  A state too large
+    for DUMP_MAX_BYTES is cut to a fixed, seeded sample of the idp-ordered particles."""
+    import numpy as np
+
+    order = np.argsort(p["idp"], kind="stable")
+    out = {"idp": p["idp"][order].astype(np.float64), "pos": p["pos"][order].astype(np.float64),
+           "vel": p["vel"][order].astype(np.float32), "rhop": p["rhop"][order].astype(np.float32),
+           "code": p["code"][order].astype(np.float32)}
+    n = len(order)
+    per = sum(a[:1].nbytes for a in out.values()) if n else 1
+    keep = DUMP_MAX_BYTES // per
+    if n > keep:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        out = {k: a[sel] for k, a in out.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + (".npy" if world == 1 else "_rank%d.npy" % rank)), a)
+
+
 def measure(case, args, rank: int, world: int, device: int, dist, use_slab: bool, steps: int, warmup: int,
-            presteps: int) -> dict:
+            presteps: int, full: bool = True, dump: str | None = None) -> dict:
     """Build the solver (one domain, or this rank's x-slab), run presteps + warmup untimed
     steps, then time exactly `steps` steps between barriers + device syncs; the elapsed
-    time is the max over ranks and the units (particles x steps) their sum."""
+    time is the max over ranks and the units (particles x steps) their sum.  `full` adds
+    the pair counts around the timed region and the per-phase breakdown after it; `dump`
+    names the directory that receives the state after the last timed step."""
     from dualsphysics_multilayer_amd.core import SphGpuSingle, SphGpuSlab, comm_unique_id, slab_partition
 
     bounds = None
@@ -287,7 +322,7 @@ def measure(case, args, rank: int, world: int, device: int, dist, use_slab: bool
         s.run(presteps + warmup)
         s.sync()
     setup_s = time.perf_counter() - t_setup
-    pairs0 = s.count_pairs()
+    pairs0 = s.count_pairs() if full else None
 
     def barrier():
         if dist is not None:
@@ -300,7 +335,7 @@ def measure(case, args, rank: int, world: int, device: int, dist, use_slab: bool
     # The timed region records HIP events around the interaction only (the roofline's launch
     # time): every timed phase puts two markers in the stream, and timing all four costs
     # ~18 us per 1M-particle Verlet step.  The per-phase breakdown comes from a second,
-    # untimed run of the same length right after.
+    # untimed run of the same length right after (--full).
     s.set_timing(True, phases=1)
     s.sync()
     barrier()
@@ -310,11 +345,16 @@ def measure(case, args, rank: int, world: int, device: int, dist, use_slab: bool
     barrier()
     elapsed = time.perf_counter() - t0
     inter_ms, nlaunch = s.timing()
-    pairs1 = s.count_pairs()
-    s.set_timing(True)
-    s.run(steps)
-    phase_ms, _ = s.timing()
-    phase_ms[0] = inter_ms[0]  # the interaction as timed inside the timed region
+    if dump:
+        dump_outputs(dump, s.particles(), rank, world)
+    pairs1 = s.count_pairs() if full else None
+    if full:
+        s.set_timing(True)
+        s.run(steps)
+        phase_ms, _ = s.timing()
+        phase_ms[0] = inter_ms[0]  # the interaction as timed inside the timed region
+    else:
+        phase_ms = [inter_ms[0], None, None, None]
     st = s.stats()
     units = float(st["np"]) * steps
     per_rank_np = [int(st["np"])]
@@ -348,6 +388,11 @@ def main() -> None:
     ap.add_argument("--bound-weight", type=float, default=0.3, help="slab balance weight of a bound particle")
     ap.add_argument("--cellmode", choices=("full", "half"), default="full",
                     help="cfg2/cfg3 cell size: full = 2h (the reference default), half = h (-cellmode:half)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: pair counts + roofline, the "
+                         "per-phase breakdown, the cfg3 and developed-flow timings, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the particle state after the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=100,
                     help="reference CPU steps timed (window 10 .. 10+K, BASELINE.md: 10-110)")
@@ -416,7 +461,8 @@ def main() -> None:
         case = WetDambreakNNCase(dp, width=CFG5_WIDTH)
     wall = {}
     t_setup = time.perf_counter()
-    m = measure(case, args, rank, world, device, dist, use_slab, args.steps, args.warmup, args.presteps)
+    m = measure(case, args, rank, world, device, dist, use_slab, args.steps, args.warmup, args.presteps,
+                full=args.full, dump=args.dump_outputs)
     wall["setup_and_warmup_s"] = m["setup_s"]
     elapsed, units, phase_ms, nlaunch = m["elapsed"], m["units"], m["phase_ms"], m["nlaunch"]
     pairs0, pairs1, st, bounds, per_rank_np, slab_info = (m["pairs0"], m["pairs1"], m["st"], m["bounds"],
@@ -426,7 +472,8 @@ def main() -> None:
     # time it beside the headline line -- on one GPU as `cfg3_1gpu`, on N ranks as
     # `strong_scaling_cfg3` -- so one scaling run yields the 1 -> N strong-scaling ratio.
     cfg3_extra = None
-    if args.workload == "cfg2" and not args.no_cfg3 and args.dp is None and args.cellmode == "full":
+    if (args.full and args.workload == "cfg2" and not args.no_cfg3 and args.dp is None
+            and args.cellmode == "full"):
         t3 = time.perf_counter()
         c3 = DamBreakCase(CFG3_DP, step_algorithm=2, tdensity=1)
         a3 = argparse.Namespace(**vars(args))
@@ -449,8 +496,8 @@ def main() -> None:
     # The flow after --developed-presteps steps (the surge under way: more particles change
     # cells, so the incremental divide does more work than in the first steps from rest).
     developed = None
-    if (args.workload == "cfg2" and world == 1 and not args.force_slab and args.developed_presteps > 0
-            and args.presteps < args.developed_presteps):
+    if (args.full and args.workload == "cfg2" and world == 1 and not args.force_slab
+            and args.developed_presteps > 0 and args.presteps < args.developed_presteps):
         t4 = time.perf_counter()
         m4 = measure(case, args, rank, world, device, dist, False, args.steps, args.warmup, args.developed_presteps)
         developed = {"presteps": args.developed_presteps, "steps": args.steps,
@@ -461,7 +508,10 @@ def main() -> None:
                      "divide_ms_per_call": float(m4["phase_ms"][2]), "wall_s": time.perf_counter() - t4}
 
     if rank == 0:
-        pairs = (pairs0.astype("float64") + pairs1.astype("float64")) / 2.0
+        if args.full:
+            pairs = (pairs0.astype("float64") + pairs1.astype("float64")) / 2.0
+        else:  # not counted: the roofline and the phases but the interaction are dropped below
+            pairs, phase_ms = [0.0] * 6, [phase_ms[0], 0.0, 0.0, 0.0]
         ff_chk, ff_real, fb_chk, fb_real, bf_chk, bf_real = pairs
         nn = args.workload == "cfg5"
         fpair, fbound = (FLOP_NN_PAIR, FLOP_NN_BOUND_PAIR) if nn else (FLOP_REAL_FLUID_PAIR, FLOP_REAL_BOUND_PAIR)
@@ -478,8 +528,9 @@ def main() -> None:
                  ["sphx::k_fluid_tiled%s<%d, %s, %d>" % (w4, td, ftb, case.cellmode)
                   for td in ((case.tdensity | 8, case.tdensity) if case.tdensity >= 2 else (case.tdensity,))
                   for w4 in ("", "_w4")])  # _w4: the 4-wave register budget (DDT1)
-        traffic = profiled_traffic(kname, case.np, "BASELINE " + args.workload) if world == 1 else None
-        vflop = profiled_valu_flop(kname, case.np, "BASELINE " + args.workload) if world == 1 else None
+        prof = args.full and world == 1
+        traffic = profiled_traffic(kname, case.np, "BASELINE " + args.workload) if prof else None
+        vflop = profiled_valu_flop(kname, case.np, "BASELINE " + args.workload) if prof else None
         res = {
             "metric": METRIC,
             "value": value,
@@ -566,7 +617,10 @@ def main() -> None:
             "cpu_baseline": None,
         }
         wall["timed_s"] = elapsed
-        if not args.no_cpu_baseline and world == 1:
+        if not args.full:
+            res["roofline"] = None
+            res["phase_ms_per_call"] = {"interaction": inter_ms, "update": None, "divide": None, "mdbc": None}
+        if args.full and not args.no_cpu_baseline and world == 1:
             # The reference at its best on the CPUs this job may use: min(usable CPUs, 64) threads
             # (it caps OpenMP at OMP_MAXTHREADS=64, OmpDefs.h:39; usable = affinity capped by the
             # cgroup quota, 16 on the GPU box) -> `value`; beside it, on a shorter window, the
@@ -596,6 +650,8 @@ def main() -> None:
             wall["cpu_baseline_s"] = time.perf_counter() - t_cpu
         wall["process_s"] = time.perf_counter() - T_START
         res["wall_breakdown"] = wall
+        res["full"] = args.full
+        res["dump_outputs"] = args.dump_outputs
         res["cfg3_1gpu" if world == 1 else "strong_scaling_cfg3"] = cfg3_extra
         if developed is not None:
             res["developed_flow"] = developed

@@ -6,7 +6,7 @@
 #      (separate passes: FETCH_SIZE and WRITE_SIZE do not fit one TCC pass,
 #       MI355X_MICROARCH.md §rocprofv3; never combined with sys/runtime traces)
 #   (PMC=1: the counter passes of pmc_passes.sh                -> <tag>/pmc/counters.json)
-#   4. bench.py (default flags, incl. the CPU baseline)        -> <tag>/bench.json
+#   4. bench.py --full (incl. the CPU baseline)                -> <tag>/bench.json
 #   (the profiled passes 1-3 skip bench.py's extra cfg3 timing and its developed-flow run:
 #    --no-cfg3 --developed-presteps 0; 8000 more steps under --pmc overran the tool's buffers)
 #      (reads the traffic of step 2-3 from profiles/<tag>/)
@@ -33,7 +33,7 @@ if [ -n "${PMC:-}" ]; then
   mkdir -p "$DST/pmc"
   python3 "$R/profiles/pmc_summary.py" "$OUT/pmc" "$DST/pmc/counters.json" > "$DST/pmc/counters.txt"
 fi
-timeout -k 10 400 python3 "$R/bench.py" $ARGS > "$OUT/bench.log" 2>&1
+timeout -k 10 400 python3 "$R/bench.py" $ARGS --full > "$OUT/bench.log" 2>&1
 grep '^{' "$OUT/bench.log" | tail -1 > "$DST/bench.json"
 mkdir -p "$R/gpurun_out/profiles/$TAG"
 cp -r "$DST"/* "$R/gpurun_out/profiles/$TAG/"

@@ -26,7 +26,7 @@ def test_bench_two_ranks_emits_weak_and_strong_scaling_lines():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--transport", "shm", "--ranks-per-gpu", "2", "--steps", "3", "--warmup", "1",
-           "--cfg3-steps", "2", "--no-cpu-baseline", "--developed-presteps", "0", "--repartition", "0"]
+           "--full", "--cfg3-steps", "2", "--no-cpu-baseline", "--developed-presteps", "0", "--repartition", "0"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
