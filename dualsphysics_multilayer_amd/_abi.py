@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-SPH_ABI_VERSION = 12
+SPH_ABI_VERSION = 13
 
 SPH_STATUS = {
     0: "SPH_OK",
@@ -396,6 +396,40 @@ class SphFloatingState(C.Structure):
         return {k: np.array(getattr(self, k)) for k in ("center", "fvel", "fomega", "angles", "facelin", "faceang")}
 
 
+SPH_GAUGE_VEL, SPH_GAUGE_SWL, SPH_GAUGE_MAXZ, SPH_GAUGE_FORCE = 0, 1, 2, 3
+GAUGE_TYPES = {"velocity": SPH_GAUGE_VEL, "swl": SPH_GAUGE_SWL, "maxz": SPH_GAUGE_MAXZ, "force": SPH_GAUGE_FORCE}
+SPH_FLAG_GAUGE_FULL = 64
+
+
+class SphGaugeDef(C.Structure):
+    _fields_ = [
+        ("type", C.c_int32), ("output", C.c_int32),
+        ("computestart", C.c_double), ("computeend", C.c_double), ("computedt", C.c_double),
+        ("outputstart", C.c_double), ("outputend", C.c_double), ("outputdt", C.c_double),
+        ("point0", C.c_double * 3), ("point2", C.c_double * 3), ("pointdir", C.c_double * 3),
+        ("height", C.c_double), ("pointnp", C.c_uint32), ("masslimit", C.c_float), ("distlimit", C.c_float),
+        ("code", C.c_uint32),
+    ]
+
+
+class SphGaugeRecord(C.Structure):
+    _fields_ = [("time", C.c_double), ("gauge", C.c_uint32), ("v", C.c_float * 3)]
+
+
+# numpy view of SphGaugeRecord[]
+GAUGE_RECORD_DTYPE = np.dtype([("time", np.float64), ("gauge", np.uint32), ("v", np.float32, 3)])
+
+
+def gauge_array(gauges: list):
+    """SphGaugeDef[] of a case's gauges (XmlCase.gauges: dicts with the struct's fields; type by name)."""
+    arr = (SphGaugeDef * max(1, len(gauges)))()
+    for i, g in enumerate(gauges):
+        _fill(arr[i], {k: v for k, v in g.items() if k != "type"})
+        arr[i].type = GAUGE_TYPES[g["type"]]
+        arr[i].output = int(bool(g.get("output", False)))
+    return arr
+
+
 def _fill(struct, d: dict):
     for k, v in d.items():
         if k not in dict(struct._fields_):
@@ -483,4 +517,6 @@ def check_struct_sizes() -> dict:
         "SphMotionEvent": C.sizeof(SphMotionEvent),
         "SphFloatingDef": C.sizeof(SphFloatingDef),
         "SphFloatingState": C.sizeof(SphFloatingState),
+        "SphGaugeDef": C.sizeof(SphGaugeDef),
+        "SphGaugeRecord": C.sizeof(SphGaugeRecord),
     }

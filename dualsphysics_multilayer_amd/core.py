@@ -31,6 +31,11 @@ from ._abi import (
     SphSlabInfo,
     SphFloatingDef,
     SphFloatingState,
+    SphGaugeDef,
+    SphGaugeRecord,
+    GAUGE_RECORD_DTYPE,
+    SPH_FLAG_GAUGE_FULL,
+    gauge_array,
     SphMotionEvent,
     SphMotionMov,
     SphMotionObj,
@@ -99,6 +104,9 @@ EXPORTED_SYMBOLS = (
     "sph_extra_normals_read",
     "sph_extra_normals_write",
     "sph_download_normals",
+    "sph_solver_set_gauges",
+    "sph_solver_gauge_records",
+    "sph_solver_measure",
 )
 
 
@@ -186,6 +194,9 @@ def load_library(path: str = LIB_PATH):
     L.sph_extra_normals_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32,
                                           C.c_uint32, C.c_int32, C.c_uint32, vp]
     L.sph_download_normals.argtypes = [vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
+    L.sph_solver_set_gauges.argtypes = [vp, C.c_uint32, C.POINTER(SphGaugeDef), C.c_uint32]
+    L.sph_solver_gauge_records.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.sph_solver_measure.argtypes = [vp, vp, C.c_uint32]
     if L.sph_abi_version() != SPH_ABI_VERSION:
         raise SphError(3, "ABI version mismatch")
     _lib = L
@@ -364,6 +375,35 @@ class SphGpuSingle:
         out = (SphFloatingState * max(1, n.value))()
         _check(load_library().sph_solver_floatings(self._h, n.value, out, C.byref(n)))
         return [out[i].as_dict() for i in range(n.value)]
+
+    # -- gauges (JDsGaugeSystem) ---------------------------------------------
+    def set_gauges(self, gauges: list, record_capacity: int = 1 << 16) -> None:
+        """Configure the gauges (XmlCase.gauges dicts) before the first step (after set_time on a
+        restart); the measure of the current TimeStep is taken at once."""
+        arr = gauge_array(gauges)
+        _check(load_library().sph_solver_set_gauges(self._h, len(gauges), arr, int(record_capacity)))
+        self.ngauges = len(gauges)
+        self.gauge_capacity = int(record_capacity)
+
+    def gauge_records(self) -> np.ndarray:
+        """Drains the device record buffer: records (GAUGE_RECORD_DTYPE) in the order taken."""
+        L = load_library()
+        n = C.c_uint32()
+        _check(L.sph_solver_gauge_records(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, GAUGE_RECORD_DTYPE)
+        assert out.itemsize == C.sizeof(SphGaugeRecord)
+        _check(L.sph_solver_gauge_records(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out[:n.value]
+
+    def gauge_overflow(self) -> bool:
+        """A record was dropped because the buffer was full (error_flags bit SPH_FLAG_GAUGE_FULL)."""
+        return bool(self.stats()["error_flags"] & SPH_FLAG_GAUGE_FULL)
+
+    def measure(self) -> np.ndarray:
+        """Every gauge evaluated now on the current state (schedules ignored and unchanged)."""
+        out = np.zeros(self.ngauges, GAUGE_RECORD_DTYPE)
+        _check(load_library().sph_solver_measure(self._h, out.ctypes.data, self.ngauges))
+        return out
 
     def save_part(self, path: str, cpart: int, head_path: str | None = None) -> None:
         """SaveData: this solver's state as a reference PART file (+ Part_Head.ibi4)."""

@@ -171,6 +171,19 @@ int sph_solver_floatings(SphSolver* s, uint32_t cap, SphFloatingState* out, uint
     if (nft) *nft = n;
   });
 }
+int sph_solver_set_gauges(SphSolver* s, uint32_t n, const SphGaugeDef* defs, uint32_t record_capacity) {
+  NEED(s && defs && n);
+  return guard([&] { s->impl->SetGauges(n, defs, record_capacity); });
+}
+int sph_solver_gauge_records(SphSolver* s, SphGaugeRecord* out, uint32_t cap, uint32_t* count) {
+  NEED(s && count);
+  return guard([&] { *count = s->impl->GaugeRecords(out, cap); });
+}
+int sph_solver_measure(SphSolver* s, SphGaugeRecord* out, uint32_t n) {
+  NEED(s && out);
+  NOT_MEMBER(s);
+  return guard([&] { s->impl->Measure(out, n); });
+}
 int sph_partfloat_write(const char* path, const char* app, uint32_t mkboundfirst, uint32_t nft,
                         const uint16_t* mkbound, const uint32_t* begin, const uint32_t* count, const float* mass,
                         const float* massp, const float* radius, uint32_t nparts, const uint32_t* cpart,

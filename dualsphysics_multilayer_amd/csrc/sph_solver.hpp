@@ -17,6 +17,7 @@
 
 #include "../../include/sphcore.h"
 #include "sph_comm.hpp"
+#include "sph_gauge.hpp"
 #include "sph_kernels.hpp"
 
 namespace sphx {
@@ -128,6 +129,13 @@ class SphGpuSingle {
   unsigned RepartitionCount() const { return repart_count_; }
   double LastImbalance() const { return repart_last_imbalance_; }
   unsigned Floatings(SphFloatingState* out, unsigned cap);
+  // Gauges (sph_gauge.hip): configured once, before the first step (after SetTime on a
+  // restart); takes the measure of the current TimeStep (JSphCpuSingle.cpp:1070).
+  void SetGauges(unsigned n, const SphGaugeDef* defs, unsigned record_capacity);
+  // Records taken since the last drain (out nullptr: their number only, nothing drained).
+  unsigned GaugeRecords(SphGaugeRecord* out, unsigned cap);
+  // Every gauge evaluated now on the current state; schedules and records untouched.
+  void Measure(SphGaugeRecord* out, unsigned n);
 
   SphConstants C{};
   KConst K{};
@@ -156,6 +164,7 @@ class SphGpuSingle {
   void Repartition();
   void RunMotion();                 // JSphCpu::RunMotion after ComputeStep (JSphCpuSingle.cpp:1096)
   void RunFloating(bool predictor); // JSphCpuSingle::RunFloating
+  void RunGauges();                 // JSphCpuSingle::RunGaugeSystem(TimeStep + stepdt) (JSphCpuSingle.cpp:1095)
   void TimedBegin(int phase);
   void TimedEnd(int phase);
 
@@ -259,6 +268,7 @@ class SphGpuSingle {
   unsigned nftp_ = 0;            // floating particles of the case (CaseNfloat)
   unsigned casenpb_ = 0;         // CaseNpb: first floating idp
   bool stepped_ = false;         // a step was issued (bodies are configured before it)
+  GaugeSet gauges_;              // the gauges (ng = 0: none; nothing is allocated or launched)
   // turns measurement mode: the dt maxima of the next DtVariable are folded at the end of the
   // interaction's turn (fold_turn_: its clear flag, -1 none), so that k_fold runs alone on the
   // GPU as on a rank's own; folded_ready_: DtVariable finds them folded

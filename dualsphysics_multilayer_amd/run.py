@@ -37,6 +37,7 @@ import time
 import numpy as np
 
 from .core import SphGpuSingle, case_derive, write_part, write_part_head
+from .gauges import GaugeCsv, max_batch
 from .xmlcase import CaseError, XmlCase
 
 
@@ -125,7 +126,8 @@ class CaseRun:
 
     def __init__(self, case: XmlCase, dirout: str, *, device: int = 0, nsteps_break: int = 0,
                  sv_all_steps: bool = False, sv_pos_double: bool = False, save: bool = True,
-                 app_name: str = "dualsphysics_multilayer_amd", log=None, sv_extra_parts: str | None = None):
+                 app_name: str = "dualsphysics_multilayer_amd", log=None, sv_extra_parts: str | None = None,
+                 gauge_capacity: int = 1 << 16, solver=None):
         self.case = case
         self.dirout = dirout
         self.nsteps_break = int(nsteps_break)
@@ -135,9 +137,19 @@ class CaseRun:
         self.app_name = app_name
         self.log = log if log is not None else (lambda s: print(s, flush=True))
         self.k = case_derive(case.case_def())
-        self.solver = SphGpuSingle(case, device=device)
+        self.solver = solver if solver is not None else SphGpuSingle(case, device=device)
         if case.time0 or case.symdtpre0:
             self.solver.set_time(case.time0, case.symdtpre0)
+        # <special><gauges>: evaluated and recorded on the device every step; the records are
+        # drained after every batch and written as the reference's Gauges*.csv
+        self.gauges = list(getattr(case, "gauges", None) or [])
+        self._gcsv = None
+        self._gbatch = 1 << 30
+        if self.gauges:
+            self._gbatch = max_batch(int(gauge_capacity), self.gauges)
+            self.solver.set_gauges(self.gauges, int(gauge_capacity))
+            os.makedirs(dirout, exist_ok=True)
+            self._gcsv = GaugeCsv(self.gauges, dirout)
         # JSph::ConfigRunMode / LoadCaseConfig: NpMinimum=CaseNp-unsigned(PartsOutMax*CaseNfluid)
         self.npminimum = case.case_np - int(np.float32(case.partsoutmax) * np.float32(case.case_nfluid))
         self.output = OutputTime(case.timeout)
@@ -172,8 +184,15 @@ class CaseRun:
                     gravity=[float(np.float32(g)) for g in c.gravity], mkbound=fb[0]["mk"], mkfluid=fl[0]["mk"],
                     symmetry=int(cd.get("symmetry", 0)))  # JPartDataHead::ConfigSymmetry (JSph.cpp:2391)
 
+    def _drain_gauges(self) -> None:
+        if self._gcsv is not None:
+            self._gcsv.add(self.solver.gauge_records())
+
     def _save(self, cpart: int, step: int) -> dict:
         st = self.solver.stats()
+        if self._gcsv is not None:  # JSph::SaveData -> GaugeSystem->SaveResults(Part)
+            self._drain_gauges()
+            self._gcsv.flush()
         nout = int(st["nout"]) - self._nout_prev
         self._nout_prev = int(st["nout"])
         info = dict(cpart=cpart, time=float(st["time"]), step=step, np=int(st["np"]), nout=nout)
@@ -241,9 +260,11 @@ class CaseRun:
                 n = max(1, math.ceil(q)) if q > 0 else 1
             if self.nsteps_break:
                 n = min(n, self.nsteps_break - nstep)
+            n = min(n, self._gbatch)  # the records of n steps fit the (drained) gauge buffer
             tprev = t
             self.solver.run(n)
             st = self.solver.stats()  # synchronises
+            self._drain_gauges()
             t = float(st["time"])
             if n > 1 and (t >= tnext or t >= tmax):
                 raise RuntimeError(f"a batch of {n} steps crossed an output time ({tprev} -> {t}, dt_cap {cap})")
@@ -260,6 +281,8 @@ class CaseRun:
                 tnext = t if sv else self.output.next_time(t)
             if self.nsteps_break and nstep >= self.nsteps_break:
                 break
+        if self._gcsv is not None:
+            self._gcsv.flush()
         self.elapsed = time.perf_counter() - t0
         self.nsteps = nstep
         self.log(f"Simulation finished: {nstep} steps, t={t:.6f} s, {self.elapsed:.2f} s wall")

@@ -30,6 +30,7 @@ builds from the file order is unchanged.
 """
 from __future__ import annotations
 
+import math
 import os
 import xml.etree.ElementTree as ET
 
@@ -140,6 +141,27 @@ def _elem_bool(node, name: str) -> bool:
     if v in ("false", "0"):
         return False
     raise CaseError(f"The value of '{name}' is not a valid boolean: {v!r}")
+
+
+def _active(ele) -> bool:
+    """JXml::CheckElementActive: active="false" (or 0) switches an element off."""
+    return (ele.get("active") or "true").strip().lower() not in ("false", "0")
+
+
+def swl_points(point0, point2, pointdp: float) -> tuple[int, list]:
+    """JGaugeSwl::SetPoints (JDsGaugeItem.cpp:447-465): PointNp and PointDir of the line
+    point0 -> point2 sampled every ~pointdp (PointNp+1 points point0 + k PointDir)."""
+    v = [float(b) - float(a) for a, b in zip(point0, point2)]
+    dis = math.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+    if not (dis > 0 and pointdp > 0):
+        return 0, [0.0, 0.0, 0.0]
+    n = int(dis / pointdp)
+    if dis - (pointdp * n) >= pointdp * 0.1:
+        n += 1
+    if n < 1:
+        n += 1
+    step = dis / n
+    return n, [(c / dis) * step for c in v]  # VecUnitary(Point2 - Point0) * dp
 
 
 # ---- <simulationdomain> (JCaseEParms::CheckPosValue, JCaseEParms.cpp:283-320) ------------
@@ -337,9 +359,11 @@ class XmlCase:
         sp = ex.find("special")
         self.phases = ()
         if sp is not None:
-            for ch in sp:  # accinputs, chrono, wavepaddles, mlayerpistons, inout, gauges, ...
+            for ch in sp:  # accinputs, chrono, wavepaddles, mlayerpistons, inout, ...
                 if ch.tag == "nnphases" and self.rheology == 2:
                     continue
+                if ch.tag == "gauges":
+                    continue  # read below, once TimeMax / TimeOut and the blocks are known
                 raise CaseError(f"<special><{ch.tag}> is not supported by this core.")
         self._load_blocks(_node(ex, "particles"))
         if self.rheology == 2:  # JSph::InitMultiPhase (JSph.cpp:3137-3215 of the v5.0 solver)
@@ -359,6 +383,11 @@ class XmlCase:
             setattr(self, k, v)
         if self.tdensity == 0:
             self.ddtvalue = 0.0
+        # <special><gauges> (JSph.cpp:2137-2139: after the command line, with TimeMax / TimePart)
+        gnode = sp.find("gauges") if sp is not None else None
+        self.gauges = self._load_gauges(gnode) if gnode is not None and _active(gnode) else []
+        if self.gauges and self.rheology == 2:
+            raise CaseError("<special><gauges> with NN multiphase is not supported by this core.")
         if not self.rhopoutmin < self.rhopoutmax:  # RhopOut disabled (JSph.cpp:862-863)
             self.rhopoutmin, self.rhopoutmax = -float(np.finfo(np.float32).max), float(np.finfo(np.float32).max)
         if not self.rhopoutmin <= self.rhop0 <= self.rhopoutmax:
@@ -671,8 +700,122 @@ class XmlCase:
 
     @property
     def explicit_codes(self) -> bool:
-        """NN multiphase: the core takes the fluid block codes (the phase of each particle)."""
-        return self.rheology == 2
+        """NN multiphase: the core takes the fluid block codes (the phase of each particle).
+        A force gauge on a block other than the first fixed one needs the block codes too."""
+        return self.rheology == 2 or any(g["type"] == "force" and g["code"] != CODE_TYPE_FIXED
+                                         for g in getattr(self, "gauges", ()))
+
+    # -- JGaugeSystem::ReadXml (JDsGaugeSystem.cpp:186-275) --------------------------------------
+    def _load_gauges(self, node) -> list:
+        """The gauges of <special><gauges> as dicts with the fields of the C ``SphGaugeDef``
+        (plus name, mkbound / idbegin / count of a force target)."""
+        f32 = lambda v: float(np.float32(v))  # noqa: E731  (JXml::ReadElementFloat)
+        massfluid, dp, kh = f32(self.massfluid), float(self.dp), f32(self.h)
+
+        def common(ele, base):  # ReadXmlCommon
+            cfg = dict(base)
+            if ele is None:
+                return cfg
+            for key, tag, att, isbool in (("savevtkpart", "savevtkpart", "value", True),
+                                          ("computedt", "computedt", "value", False),
+                                          ("computestart", "computetime", "start", False),
+                                          ("computeend", "computetime", "end", False),
+                                          ("output", "output", "value", True),
+                                          ("outputdt", "outputdt", "value", False),
+                                          ("outputstart", "outputtime", "start", False),
+                                          ("outputend", "outputtime", "end", False)):
+                e = ele.find(tag)
+                if e is None or e.get(att) is None:
+                    continue
+                if isbool:
+                    v = e.get(att).strip().lower()
+                    if v not in ("true", "1", "false", "0"):
+                        raise CaseError(f"The value of '{tag}' is not a valid boolean: {v!r}")
+                    cfg[key] = v in ("true", "1")
+                else:
+                    cfg[key] = _attr_double(e, att, tag)
+            return cfg
+
+        def d3(ele, name):
+            e = ele.find(name)
+            if e is None:
+                raise CaseError(f"The item is not found '{name}'.")
+            return [_attr_double(e, a, name) for a in ("x", "y", "z")]
+
+        def which(ele, name, atts):  # JXml::CheckElementAttributes(optional, checkmanyatt)
+            e = ele.find(name)
+            if e is None:
+                return 0, None
+            found = [i + 1 for i, a in enumerate(atts) if e.get(a) is not None]
+            if len(found) > 1:
+                raise CaseError(f"<{name}>: only one of the attributes {list(atts)} is allowed.")
+            if not found:
+                raise CaseError(f"<{name}>: one of the attributes {list(atts)} is needed.")
+            return found[0], f32(_attr_double(e, atts[found[0] - 1], name))
+
+        # ResetCfgDefault (JDsGaugeSystem.cpp:83-93)
+        default = dict(savevtkpart=False, computedt=self.timeout, computestart=0.0, computeend=self.timemax,
+                       output=False, outputdt=self.timeout, outputstart=0.0, outputend=self.timemax)
+        default = common(node.find("default"), default)
+        gauges, vtk = [], False
+        for ele in node:
+            cmd = ele.tag
+            if not isinstance(cmd, str) or not cmd or cmd[0] == "_" or cmd == "default" or not _active(ele):
+                continue
+            name = ele.get("name")
+            if name is None:
+                raise CaseError(f"<gauges><{cmd}>: the attribute 'name' is missing.")
+            if any(g["name"] == name for g in gauges):
+                raise CaseError(f"The name '{name}' already exists.")
+            cfg = common(ele, default)
+            vtk = vtk or cfg.pop("savevtkpart")
+            g = dict(cfg, name=name, type=cmd, point0=[0.0] * 3, point2=[0.0] * 3, pointdir=[0.0] * 3, pointnp=0,
+                     masslimit=0.0, height=0.0, distlimit=0.0, code=0)
+            if cmd == "velocity":
+                g["point0"] = d3(ele, "point")
+            elif cmd == "swl":
+                k, v = which(ele, "masslimit", ("value", "coef"))
+                masslimit = (v if k == 1 else f32(np.float32(massfluid) * np.float32(v)) if k == 2
+                             else f32(np.float32(massfluid) * np.float32(0.4 if self.data2d else 0.5)))
+                if masslimit <= 0:
+                    raise CaseError(f"The masslimit ({masslimit:f}) is invalid.")
+                k, v = which(ele, "pointdp", ("value", "coefdp"))
+                if k == 0:
+                    raise CaseError("The item is not found 'pointdp'.")
+                pointdp = v if k == 1 else dp * v
+                if pointdp <= 0:
+                    raise CaseError(f"The pointdp ({pointdp:f}) is invalid.")
+                g["point0"], g["point2"] = d3(ele, "point0"), d3(ele, "point2")
+                g["pointnp"], g["pointdir"] = swl_points(g["point0"], g["point2"], pointdp)
+                g["pointdp"], g["masslimit"] = pointdp, masslimit
+            elif cmd == "maxz":
+                g["point0"] = d3(ele, "point0")
+                g["height"] = f32(_elem_double(ele, "height"))
+                k, v = which(ele, "distlimit", ("value", "coefdp", "coefh"))
+                if k == 0:
+                    raise CaseError("The item is not found 'distlimit'.")
+                distlimit = v if k == 1 else f32(dp * v) if k == 2 else f32(np.float32(kh) * np.float32(v))
+                if distlimit <= 0:
+                    raise CaseError(f"The distlimit ({distlimit:f}) is invalid.")
+                g["distlimit"] = distlimit
+            elif cmd == "force":
+                e = ele.find("target")
+                if e is None or e.get("mkbound") is None:
+                    raise CaseError("The item is not found 'target'.")
+                mkbound = int(e.get("mkbound"))
+                blk = [b for b in self.blocks if b["type"] != "fluid" and b["mktype"] == mkbound]
+                if not blk:
+                    raise CaseError(f"Error loading boundary objects. Mkbound={mkbound} is unknown.")
+                if blk[0]["type"] not in ("fixed", "moving"):
+                    raise CaseError(f"Type of boundary particles (Mkbound={mkbound}) is invalid. "
+                                    "Only fixed or moving particles are allowed.")
+                g.update(mkbound=mkbound, code=int(blk[0]["code"]), idbegin=blk[0]["begin"], count=blk[0]["count"])
+            else:
+                raise CaseError(f"Gauge type '{cmd}' is invalid.")
+            gauges.append(g)
+        if vtk:  # the reference built without VTK ignores it too (JVtkLib::Available)
+            print("gauges: savevtkpart is ignored (no VTK output of gauges).", flush=True)
+        return gauges
 
     # -- JCasePartBlock_Floating::ReadXml (JCaseParts.cpp:248-290) ------------------------------
     @staticmethod

@@ -53,6 +53,9 @@
  *   sph_solver_set_floating_table  FtLinearVel/FtAngularVel/FtLinearForce/FtAngularForce
  *                                (JSph.cpp:1060-1082; JSphCpuSingle.cpp:874-914)
  *   sph_solver_floatings ....... FtObjs[] (feeds PartFloat.fbi4, JPartFloatBi4)
+ *   sph_solver_set_gauges ...... JGaugeSystem (JDsGaugeSystem.cpp, JDsGaugeItem.cpp): velocity,
+ *     sph_solver_gauge_records   SWL, MaxZ and force gauges evaluated and recorded on the device
+ *     sph_solver_measure         after every step's update (RunGaugeSystem, JSphCpuSingle.cpp:1095)
  */
 #ifndef SPHCORE_H
 #define SPHCORE_H
@@ -64,7 +67,7 @@
 extern "C" {
 #endif
 
-#define SPH_ABI_VERSION 12
+#define SPH_ABI_VERSION 13
 
 typedef enum {
   SPH_OK = 0,
@@ -582,6 +585,59 @@ int sph_extra_normals_write(const char* path, const char* app, uint32_t cpart, u
  * only) and whether the floating bodies have them (UseNormalsFt) — JSphGpuSingle::SaveExtraData
  * (JSphGpuSingle.cpp:946-968). */
 int sph_download_normals(SphSolver* s, uint32_t cap, float* normals, uint32_t* n, int32_t* usenormalsft);
+
+/* ---- gauges (JDsGaugeSystem / JDsGaugeItem): measures taken on the device while the run goes
+ * on.  Each gauge has a compute schedule (Update: t >= ComputeNext and ComputeStart <= t <=
+ * ComputeEnd, then ComputeNext = the next multiple of ComputeDt after t) and an output schedule
+ * (OutputSave, OutputStart/End/Dt the same way; JDsGaugeItem.h:164-165, .cpp:204-211,266-270).
+ * After the last update of every step (JSphCpuSingle.cpp:1094-1098: before the motion and the
+ * divide, at TimeStep + stepdt) the due gauges are evaluated and, when their output is due, a
+ * record is appended to a device buffer; once more when they are configured (the row of the
+ * current TimeStep, JSphCpuSingle.cpp:1070).  Nothing of this needs the host: a batch of
+ * sph_solver_run steps records on its own and the host drains the buffer afterwards.
+ *   VEL    velocity at `point0`: sum of wab vel mass/rho over the fluid, no kernel correction;
+ *          zeros outside the domain (JGaugeVelocity::CalculeCpuT)
+ *   SWL    free surface on the line point0 -> point2: mass at the pointnp+1 points point0 +
+ *          k pointdir, first fall below masslimit after a point above it, interpolated
+ *          (JGaugeSwl::CalculeCpuT); v = the surface position
+ *   MAXZ   highest fluid particle within distlimit (horizontally) of the vertical line from
+ *          point0 of `height` (JGaugeMaxZ::CalculeCpu); v[0] = zmax
+ *   FORCE  pressure force of the fluid on the fixed or moving block of particle code `code`
+ *          (type | block index, JSphMk) (JGaugeForce::CalculeCpuT); v = the force
+ * The Wendland kernel is used whatever the case's kernel (JDsGaugeSystem.cpp:102-106); Symmetry
+ * adds no mirror images (as in the reference). */
+enum { SPH_GAUGE_VEL = 0, SPH_GAUGE_SWL = 1, SPH_GAUGE_MAXZ = 2, SPH_GAUGE_FORCE = 3 };
+typedef struct SphGaugeDef {
+  int32_t type;                 /* SPH_GAUGE_*                                     */
+  int32_t output;               /* OutputSave                                      */
+  double computestart, computeend, computedt;
+  double outputstart, outputend, outputdt;
+  double point0[3];             /* VEL: the point; SWL, MAXZ: Point0               */
+  double point2[3];             /* SWL: Point2                                     */
+  double pointdir[3];           /* SWL: PointDir (JGaugeSwl::SetPoints)            */
+  double height;                /* MAXZ: Height                                    */
+  uint32_t pointnp;             /* SWL: PointNp                                    */
+  float masslimit;              /* SWL: MassLimit                                  */
+  float distlimit;              /* MAXZ: DistLimit                                 */
+  uint32_t code;                /* FORCE: particle code of the block (type | index) */
+} SphGaugeDef;
+typedef struct SphGaugeRecord {
+  double time;                  /* TimeStep of the measure                         */
+  uint32_t gauge;               /* index in the configured list                    */
+  float v[3];                   /* result (see the types above)                    */
+} SphGaugeRecord;
+/* error_flags bit of sph_solver_stats: a record found the buffer full and was dropped (not fatal) */
+#define SPH_FLAG_GAUGE_FULL 64u
+/* Configure the gauges (single domain, single phase; once, before the first step and after
+ * sph_solver_set_time on a restart) with a record buffer of record_capacity records, and take
+ * the measure of the current TimeStep. */
+int sph_solver_set_gauges(SphSolver* s, uint32_t n, const SphGaugeDef* defs, uint32_t record_capacity);
+/* Drain the record buffer (synchronises): up to cap records in the order they were taken into
+ * out, their number in *count; the buffer is empty afterwards.  out NULL: *count only, nothing drained. */
+int sph_solver_gauge_records(SphSolver* s, SphGaugeRecord* out, uint32_t cap, uint32_t* count);
+/* Evaluate every gauge now, on the current state (synchronises): out[n], in list order.  The
+ * schedules are ignored and left unchanged, nothing is recorded. */
+int sph_solver_measure(SphSolver* s, SphGaugeRecord* out, uint32_t n);
 
 #ifdef __cplusplus
 }
