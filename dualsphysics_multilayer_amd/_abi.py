@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-SPH_ABI_VERSION = 13
+SPH_ABI_VERSION = 14
 
 SPH_STATUS = {
     0: "SPH_OK",
@@ -222,6 +222,7 @@ class SphRunStats(C.Structure):
         ("acemax", C.c_float),
         ("viscdtmax", C.c_float),
         ("viscetadtmax", C.c_float),
+        ("fused_updates", C.c_uint64),
     ]
 
     def as_dict(self) -> dict:

@@ -302,6 +302,12 @@ class SphGpuSingle:
     def Interaction_Forces(self, interstep: int = INTERSTEP_VERLET) -> None:
         _check(load_library().sph_interaction_forces(self._h, interstep))
 
+    def DtVariable(self, final: bool) -> None:
+        """DtVariable(final) where the reference calls it: False is the Symplectic predictor's,
+        True the Verlet step's and the Symplectic corrector's (Verlet with False: the maxima
+        of the last interaction only, no step)."""
+        _check(load_library().sph_compute_dt(self._h, int(bool(final))))
+
     def ComputeVerlet(self) -> None:
         _check(load_library().sph_step_verlet(self._h))
 

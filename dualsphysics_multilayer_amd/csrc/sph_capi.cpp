@@ -90,22 +90,22 @@ int sph_interaction_forces(SphSolver* s, int interstep) {
 int sph_compute_dt(SphSolver* s, int final_) {
   NEED(s);
   NOT_MEMBER(s);
-  return guard([&] { s->impl->DtVariable(final_ ? sphx::DT_VERLET : sphx::DT_PEEK); });
+  return guard([&] { s->impl->PhaseDt(final_ != 0); });
 }
 int sph_step_verlet(SphSolver* s) {
   NEED(s);
   NOT_MEMBER(s);
-  return guard([&] { s->impl->ComputeVerlet(); });
+  return guard([&] { s->impl->PhaseUpdate(1); });
 }
 int sph_step_symplectic_pre(SphSolver* s) {
   NEED(s);
   NOT_MEMBER(s);
-  return guard([&] { s->impl->ComputeSymplecticPre(); });
+  return guard([&] { s->impl->PhaseUpdate(2); });
 }
 int sph_step_symplectic_cor(SphSolver* s) {
   NEED(s);
   NOT_MEMBER(s);
-  return guard([&] { s->impl->ComputeSymplecticCorr(); });
+  return guard([&] { s->impl->PhaseUpdate(3); });
 }
 int sph_solver_run(SphSolver* s, uint32_t nsteps) {
   NEED(s);

@@ -500,6 +500,8 @@ void SphGpuSingle::Init(const SphCaseDef& cdef, const SphParticlesHost& init) {
   // again per divide for a re-partitioned slab; ncy >= 3 or a single y row), 30-bit counts
   inc_ok_ = G.ncx >= 3 && (G.ncy >= 3 || G.ncy == 1) && n < (1u << 29);
   if (const char* e = std::getenv("SPH_DIVIDE")) inc_ok_ = inc_ok_ && std::string(e) != "full";
+  if (const char* e = std::getenv("SPH_CLS_SPLIT")) cls_split_ = std::atoi(e) != 0;
+  if (cls_split_) test_hook_notice("SPH_CLS_SPLIT");
   // The tiled kernel stages the 3x3 rows of 3 cells of CellMode=full, or the 5x5 rows of
   // 5 half-cells of CellMode=half (run_pass_half).
   nn_ = (C.rheology == SPH_RHEOLOGY_NN);
@@ -1247,6 +1249,10 @@ void SphGpuSingle::RunCellDivide() {
   // and the timed divide phase is those kernels alone (the exchange waits for neighbours)
   const bool turn = slab() && exchange_armed_ && in_run_ && transport_->turns();
   if (!turn) TimedBegin(2);
+  // the update's classification was made for this divide (FuseUpdate's prediction): a phase
+  // order that breaks it must not merge with stale classes
+  if (classified_ && fuse_pre_ != havepre_)
+    throw SphError(SPH_ERR_STATE, "internal: the update classified the particles for another divide");
   if (slab() && exchange_armed_ && repart_every_ && (stepsdone_ % repart_every_) == 0 && transport_->nranks > 1 &&
       !havepre_)
     Repartition();
@@ -1530,22 +1536,20 @@ void SphGpuSingle::UpdateTurn(bool begin) {
 // incremental and nothing moves a particle between the update and the divide (no floating
 // bodies, no moving boundaries; no re-partition at that divide, which changes the slab's
 // columns and hence every key).  pre_at_divide: whether the Symplectic pre-state is held at
-// the divide (the re-partition's condition).  SPH_CLS_SPLIT=1 (test hook) keeps the separate
+// the divide (the re-partition's condition; RunCellDivide checks that it holds what was
+// predicted here).  SPH_CLS_SPLIT=1 (test hook, read at construction) keeps the separate
 // k_inc_classify and k_pack_count launches.
 SphGpuSingle::UpdateFuse SphGpuSingle::FuseUpdate(bool pre_at_divide) {
-  static const bool split = [] {
-    const bool on = std::getenv("SPH_CLS_SPLIT") && std::atoi(std::getenv("SPH_CLS_SPLIT"));
-    if (on) test_hook_notice("SPH_CLS_SPLIT");
-    return on;
-  }();
   classified_ = packcounted_ = false;
   UpdateFuse f;
   const bool repart = slab() && exchange_armed_ && repart_every_ && (stepsdone_ % repart_every_) == 0 &&
                       transport_->nranks > 1 && !pre_at_divide;
-  if (split || repart || !inc_ok_ || !inc_valid_ || !(G.ncx >= 3 && (G.ncy >= 3 || G.ncy == 1)) || nftbodies_ ||
+  if (cls_split_ || repart || !inc_ok_ || !inc_valid_ || !(G.ncx >= 3 && (G.ncy >= 3 || G.ncy == 1)) || nftbodies_ ||
       nmotobj_ || inc_.napp != 0)
     return f;
   classified_ = true;
+  fuse_pre_ = pre_at_divide;
+  fused_updates_++;
   f.cls = &inc_;
   const bool hl = slab() && transport_->has_left(), hr = slab() && transport_->has_right();
   if (slab() && exchange_armed_ && (hl || hr)) {
@@ -1620,6 +1624,29 @@ void SphGpuSingle::ComputeStep() {
   if (gauges_.ng) RunGauges();  // at TimeStep + stepdt, before the motion and the divide (JSphCpuSingle.cpp:1095)
   if (nmotobj_) RunMotion();
   RunCellDivide();
+}
+
+void SphGpuSingle::PhaseDt(bool final_) {
+  check_hip(hipSetDevice(device), "hipSetDevice");
+  if (step_algorithm_ == SPH_STEP_VERLET) DtVariable(final_ ? DT_VERLET : DT_PEEK);
+  else DtVariable(final_ ? DT_SYM_COR : DT_SYM_PRE);
+}
+
+void SphGpuSingle::PhaseUpdate(int interstep) {
+  if (nmotobj_ || nftbodies_)
+    throw SphError(SPH_ERR_UNSUPPORTED,
+                   "the update phases do not move a motion program's boundaries or floating bodies: step such a "
+                   "solver with sph_solver_run");
+  if ((interstep == 1) != (step_algorithm_ == SPH_STEP_VERLET))
+    throw SphError(SPH_ERR_STATE, "the update phase is not one of the solver's step algorithm");
+  check_hip(hipSetDevice(device), "hipSetDevice");
+  // ComputeStep's bookkeeping, once per step: stepsdone_ is read by this update's FuseUpdate
+  // and by the divides after it (a slab's re-partition schedule), as inside ComputeStep
+  stepped_ = true;
+  if (interstep != 3) stepsdone_++;
+  if (interstep == 1) ComputeVerlet();
+  else if (interstep == 2) ComputeSymplecticPre();
+  else ComputeSymplecticCorr();
 }
 
 // ---- gauges (sph_gauge.hip) ----------------------------------------------------------------
@@ -2142,6 +2169,7 @@ SphRunStats SphGpuSingle::Stats() {
   r.acemax = s.last_acemax;
   r.viscdtmax = s.last_viscdt;
   r.viscetadtmax = s.last_visceta;
+  r.fused_updates = fused_updates_;
   return r;
 }
 

@@ -86,6 +86,14 @@ class SphGpuSingle {
   // Whole steps: ComputeStep_Ver / ComputeStep_Sym + RunCellDivide (JSphGpuSingle.cpp:548-596,853-880).
   void ComputeStep();
   void Run(unsigned nsteps);
+  // The phases as a host loop reaches them through the C ABI (sph_compute_dt, sph_step_*).
+  // PhaseDt: DtVariable(final) where the reference calls it (the Symplectic predictor with
+  // false, the Verlet step and the Symplectic corrector with true).  PhaseUpdate(interstep):
+  // ComputeVerlet (1) / ComputeSymplecticPre (2) / ComputeSymplecticCorr (3) with the step
+  // bookkeeping of ComputeStep; refused with bodies or a motion program, which only
+  // ComputeStep moves.
+  void PhaseDt(bool final_);
+  void PhaseUpdate(int interstep);
 
   void Sync();
   SphRunStats Stats();
@@ -247,6 +255,9 @@ class SphGpuSingle {
   double* motdata_ = nullptr;  // rows of the file movements' tables (4 doubles each)
   bool classified_ = false;     // the last update classified the particles for the divide
   bool packcounted_ = false;    // ... and ran the slab exchange's count pass
+  bool fuse_pre_ = false;       // ... for a divide that holds the Symplectic pre-state (checked there)
+  bool cls_split_ = false;      // SPH_CLS_SPLIT test hook: never, the divide and the exchange do both
+  unsigned long long fused_updates_ = 0;  // updates that classified (SphRunStats.fused_updates)
   PackArgs pack_args_;
   struct UpdateFuse {
     const IncDivScratch* cls = nullptr;

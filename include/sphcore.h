@@ -67,7 +67,7 @@
 extern "C" {
 #endif
 
-#define SPH_ABI_VERSION 13
+#define SPH_ABI_VERSION 14
 
 typedef enum {
   SPH_OK = 0,
@@ -248,6 +248,9 @@ typedef struct SphRunStats {
   uint32_t error_flags;   /* bit0: NaN/inf dt, bit1: boundary out           */
   float velmax, acemax, viscdtmax; /* of the last interaction              */
   float viscetadtmax;     /* NN: max effective viscosity (ViscEtaDtMax)     */
+  uint64_t fused_updates; /* update launches that also classified the particles
+                             for the next divide (0 with SPH_CLS_SPLIT=1, bodies,
+                             motion or SPH_DIVIDE=full: the divide classifies)  */
 } SphRunStats;
 
 /* Host particle view (SaveData layout: JSph::SaveData, JSph.cpp:2717). */
@@ -283,13 +286,31 @@ int sph_case_derive(const SphCaseDef* cdef, SphConstants* out);
 int sph_solver_create(const SphCaseDef* cdef, const SphParticlesHost* init, int device, SphSolver** out);
 int sph_solver_destroy(SphSolver* s);
 
-/* ---- hot path: individual phases (all async on the solver stream) -------- */
+/* ---- hot path: individual phases (all async on the solver stream) --------
+ * A host loop that steps through these follows ComputeStep_Ver / ComputeStep_Sym
+ * (JSphCpuSingle.cpp:674-720) and ends each step with sph_divide, as sph_solver_run does:
+ *   Verlet:      interaction_forces(1), compute_dt(1), step_verlet, divide
+ *   Symplectic:  interaction_forces(2), compute_dt(0), step_symplectic_pre, divide,
+ *                interaction_forces(3), compute_dt(1), step_symplectic_cor, divide
+ * and gives the state of sph_solver_run bit for bit; the two may be mixed between steps.
+ * sph_compute_dt(final) is DtVariable(final) where the reference calls it:
+ *   Symplectic, final = 0: the predictor's dt (the step runs with SymplecticDtPre; TimeStep
+ *                          and the step count advance here),
+ *   Symplectic, final = 1: the corrector's dt (SymplecticDtPre = min of the two),
+ *   Verlet,     final = 1: the step's dt (TimeStep and the step count advance),
+ *   Verlet,     final = 0: the maxima of the last interaction only (SphRunStats), no step.
+ * The three update calls count as a step (configuration calls "before the first step" are
+ * refused after them).  They do not move bodies: a solver with a motion program or floating
+ * bodies refuses them with SPH_ERR_UNSUPPORTED (RunMotion / RunFloating run inside
+ * sph_solver_run only).  Gauges: sph_solver_measure is the phase-level form; the scheduled
+ * records are taken by sph_solver_run.  sph_divide may be called at any time between phases;
+ * a divide that follows no update leaves the state as it is. */
 int sph_divide(SphSolver* s);                       /* RunCellDivide(true)        */
 int sph_interaction_forces(SphSolver* s, int interstep); /* 1 Verlet, 2 SymPre, 3 SymCor */
-int sph_compute_dt(SphSolver* s, int final_);       /* DtVariable(final)          */
+int sph_compute_dt(SphSolver* s, int final_);       /* DtVariable(final), see above */
 int sph_step_verlet(SphSolver* s);                  /* ComputeVerlet(dt)          */
-int sph_step_symplectic_pre(SphSolver* s);          /* ComputeSymplecticPre(dt)   */
-int sph_step_symplectic_cor(SphSolver* s);          /* ComputeSymplecticCorr(dt)  */
+int sph_step_symplectic_pre(SphSolver* s);          /* ComputeSymplecticPre(SymplecticDtPre) */
+int sph_step_symplectic_cor(SphSolver* s);          /* ComputeSymplecticCorr(SymplecticDtPre) */
 
 /* ---- hot path: whole steps (ComputeStep + RunCellDivide), device-resident -- */
 int sph_solver_run(SphSolver* s, uint32_t nsteps);

@@ -7,8 +7,10 @@
 // sph_download_particles, and write the state as reference PART files (sph_part_write),
 // which tests/test_cpp_host.py compares with the reference's own PARTs.
 //
-//   host_loop <case path without extension> <outdir> <step1> [<step2> ...]
+//   host_loop [--phases] <case path without extension> <outdir> <step1> [<step2> ...]
 //   -> <outdir>/Part_0001.bi4 after step1 steps, Part_0002.bi4 after step2, ...
+// --phases steps with the phase calls (ComputeStep_Ver / ComputeStep_Sym of JSphCpuSingle.cpp:
+// 674-720 + the divide that ends a step) instead of sph_solver_run; the PARTs are the same.
 //
 // Build: g++ -O2 -std=c++17 -I<repo>/include host_loop.cpp -L<repo>/dualsphysics_multilayer_amd/lib
 //        -lsphcore -Wl,-rpath,<repo>/dualsphysics_multilayer_amd/lib -o host_loop
@@ -57,9 +59,34 @@ struct CaseXml {
   }
 };
 
+// One step through the phase-level calls, as the host's own ComputeStep would issue them.
+static void StepByPhases(SphSolver* s, int step_algorithm) {
+  if (step_algorithm == SPH_STEP_VERLET) {
+    Check(sph_interaction_forces(s, 1), "Interaction_Forces");
+    Check(sph_compute_dt(s, 1), "DtVariable(true)");
+    Check(sph_step_verlet(s), "ComputeVerlet");
+    Check(sph_divide(s), "RunCellDivide");
+  } else {
+    Check(sph_interaction_forces(s, 2), "Interaction_Forces");
+    Check(sph_compute_dt(s, 0), "DtVariable(false)");
+    Check(sph_step_symplectic_pre(s), "ComputeSymplecticPre");
+    Check(sph_divide(s), "RunCellDivide");
+    Check(sph_interaction_forces(s, 3), "Interaction_Forces");
+    Check(sph_compute_dt(s, 1), "DtVariable(true)");
+    Check(sph_step_symplectic_cor(s), "ComputeSymplecticCorr");
+    Check(sph_divide(s), "RunCellDivide");
+  }
+}
+
 int main(int argc, char** argv) {
+  const char* prog = argv[0];
+  const bool phases = argc > 1 && std::strcmp(argv[1], "--phases") == 0;
+  if (phases) {
+    argc--;
+    argv++;
+  }
   if (argc < 4) {
-    std::fprintf(stderr, "usage: %s <case> <outdir> <step1> [step2 ...]\n", argv[0]);
+    std::fprintf(stderr, "usage: %s [--phases] <case> <outdir> <step1> [step2 ...]\n", prog);
     return 2;
   }
   try {
@@ -120,7 +147,11 @@ int main(int argc, char** argv) {
     uint32_t done = 0;
     for (int a = 3; a < argc; a++) {
       const uint32_t target = uint32_t(std::atoi(argv[a]));
-      if (target > done) Check(sph_solver_run(s, target - done), "run");
+      if (phases) {
+        for (uint32_t k = done; k < target; k++) StepByPhases(s, cd.step_algorithm);
+      } else if (target > done) {
+        Check(sph_solver_run(s, target - done), "run");
+      }
       done = target;
       SphRunStats st;
       Check(sph_solver_stats(s, &st), "stats");  // synchronises

@@ -5,7 +5,9 @@ The host loads a dam-break case written by the reference-side generator
 (oracle/tools/gencase_ref), derives SphCaseDef as JSph::LoadCaseConfig/LoadCaseParticles
 do, runs sph_solver_run and writes reference PART files with sph_part_write; the PARTs
 must match the reference solver's own PARTs of that case (tests/golden, 10x its noise
-floor) and be readable by the reference's reader."""
+floor) and be readable by the reference's reader.  With --phases the host steps through the
+phase calls instead (sph_interaction_forces, sph_compute_dt, sph_step_*, sph_divide): the
+same PARTs, bit for bit, for a Verlet and a Symplectic case."""
 import os
 import subprocess
 
@@ -60,3 +62,36 @@ def test_host_loop_parts_match_reference(tmp_path):
     dump = tmp_path / "p.bin"
     subprocess.check_call([os.path.join(REF, "partdump_ref"), str(out), "2", str(dump)], stdout=subprocess.DEVNULL)
     assert dump.stat().st_size > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,step,ddt", [("verlet_ddt2_dp0.02", 1, 2), ("symplectic_ddt1_dp0.025", 2, 1)])
+def test_host_loop_phases_are_run(tmp_path, name, step, ddt):
+    """host_loop --phases steps with sph_interaction_forces / sph_compute_dt / sph_step_* /
+    sph_divide (the reference's ComputeStep sequence) instead of sph_solver_run: the PARTs hold
+    the same bits, and they match the reference's own PARTs as the run's do."""
+    from dualsphysics_multilayer_amd.core import read_part
+
+    exe = EXE if os.path.exists(EXE) else build_host(str(tmp_path / "host_loop"))
+    g = load(name)
+    dp = repr(float(g["meta"][0]))
+    subprocess.check_call([os.path.join(REF, "gencase_ref"), dp, str(tmp_path), str(step), str(ddt), "1.5",
+                           "CaseDambreak", "1"], stdout=subprocess.DEVNULL)
+    parts = {}
+    for mode in ("run", "phases"):
+        out = tmp_path / mode
+        out.mkdir()
+        r = subprocess.run([exe] + (["--phases"] if mode == "phases" else []) +
+                           [str(tmp_path / "CaseDambreak"), str(out), "1", "10"], capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 0, r.stderr
+        parts[mode] = [read_part(str(out / ("Part_%04u.bi4" % cpart))) for cpart in (1, 2)]
+    for (hr, pr), (hp, pp), k in zip(parts["run"], parts["phases"], (1, 10)):
+        assert hp["step"] == hr["step"] == k and hp["timestep"] == hr["timestep"]
+        for q in ("idp", "pos", "vel", "rhop"):  # file order = the solver's order
+            assert np.array_equal(pp[q], pr[q]), (k, q)
+        got, ref = by_idp(pp), snapshot(g, k)
+        assert np.array_equal(got["idp"], ref["idp"])
+        for q, t in zip(("pos", "vel", "rhop"), tol(k)):
+            assert maxdiff(got, ref, q) <= t, (k, q, maxdiff(got, ref, q))
+        assert abs(hp["timestep"] - float(ref["time"])) <= 1e-9 * k
