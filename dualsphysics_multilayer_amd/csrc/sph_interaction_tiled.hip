@@ -272,10 +272,14 @@ __device__ __forceinline__ void drain_words(const KConst& K, const P1& p, unsign
 // complement each other, so the loop length (the busiest lane's count / 2) is far closer
 // to the average lane's than with one row at a time.
 // The accepted candidates of a round (<= 128 per window) are four 64-bit words,
-// compacted once into a chain (empty words dropped): `cur` is popped, and when it runs
-// dry the next word shifts in.  Value selects only (a word picked by reference puts the
-// masks in scratch), no divergent branch in the loop (the second pop of an iteration is
-// unconditional; an empty pop's pair is masked off).
+// compacted once into a chain (empty words dropped).  An iteration takes up to two bits
+// of the chain's first word, in ascending order, and then shifts the chain ONCE if that
+// word ran dry (a shift per bit cost ~20 of the ~138 VALU instructions of an iteration;
+// a word with an odd count now leaves one pair slot of an iteration empty, ~5 % more
+// iterations: cfg2 interaction 0.582-0.591 -> 0.557-0.564 ms).  Value selects only (a word
+// picked by reference puts the masks in scratch), no divergent branch in the loop (the
+// second bit is taken unconditionally; an empty one's pair is masked off).  Every p1
+// still meets its pairs in ascending order, so the sums are unchanged.
 // SELF (the Symmetry image of the own row): staged record `self` of window a is the lane's
 // own p1, whose image is no neighbour (the reference visits an image only after its
 // original passed the rr2 >= ALMOSTZERO test, JSphCpu.cpp:687,793-796).
@@ -368,8 +372,12 @@ __device__ __forceinline__ void drain_words(const KConst& K, const P1& p, unsign
     b1 <<= 4;
     b2 <<= 4;
     b3 <<= 4;
-    auto pop = [&](void) -> int {
-      const int j = b0 + (int(__builtin_ctzll(c0 | (1ull << 63))) << 4);
+    while (c0) {
+      // up to two bits of the current word, then ONE shift of the chain
+      const int j1 = b0 + (int(__builtin_ctzll(c0)) << 4);
+      c0 &= c0 - 1ull;
+      const bool two = c0 != 0ull;
+      const int j2 = two ? b0 + (int(__builtin_ctzll(c0 | (1ull << 63))) << 4) : j1;
       c0 &= c0 - 1ull;
       const bool e = c0 == 0ull;
       c0 = e ? c1 : c0;
@@ -379,13 +387,6 @@ __device__ __forceinline__ void drain_words(const KConst& K, const P1& p, unsign
       c2 = e ? c3 : c2;
       b2 = e ? b3 : b2;
       c3 = e ? 0ull : c3;
-      return j;
-    };
-    while (c0) {
-      const int j1 = pop();
-      const bool two = c0 != 0ull;
-      const int j2p = pop();
-      const int j2 = two ? j2p : j1;
       const float4 A1 = *at16(sA, j1), A2 = *at16(sA, j2);
       const float4 B1 = *at16(sB, j1), B2 = *at16(sB, j2);
       const typename CRecT<FT>::type C1 = at_rec(sC, j1), C2 = at_rec(sC, j2);
