@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-SPH_ABI_VERSION = 14
+SPH_ABI_VERSION = 15
 
 SPH_STATUS = {
     0: "SPH_OK",
@@ -431,6 +431,93 @@ def gauge_array(gauges: list):
     return arr
 
 
+SPH_MAX_ACCINPUTS = SPH_MAX_DAMPINGS = 16
+SPH_DAMP_PLANE, SPH_DAMP_BOX, SPH_DAMP_CYLINDER = 0, 1, 2
+DAMP_TYPES = {"plane": SPH_DAMP_PLANE, "box": SPH_DAMP_BOX, "cylinder": SPH_DAMP_CYLINDER}
+# JDsDampingOp_Box::TpDirections (JDsDamping.h:169-179)
+DAMP_DIRS = {"top": 1, "bottom": 2, "left": 4, "right": 8, "front": 16, "back": 32, "all": 63}
+
+
+class SphAccInputDef(C.Structure):
+    _fields_ = [
+        ("code1", C.c_uint32), ("code2", C.c_uint32), ("globalgravity", C.c_int32),
+        ("row0", C.c_uint32), ("nrows", C.c_uint32), ("pad", C.c_uint32),
+        ("timestart", C.c_double), ("timeend", C.c_double), ("centre", C.c_double * 3),
+    ]
+
+
+class SphDampingDef(C.Structure):
+    _fields_ = [
+        ("type", C.c_int32), ("usedomain", C.c_int32), ("directions", C.c_uint32),
+        ("overlimit", C.c_float), ("redumax", C.c_float), ("factorxyz", C.c_float * 3),
+        ("pt", (C.c_double * 3) * 4), ("dompt", (C.c_double * 2) * 4),
+        ("domzmin", C.c_double), ("domzmax", C.c_double), ("radmin", C.c_double), ("radmax", C.c_double),
+    ]
+
+
+class SphDampingDerived(C.Structure):
+    _fields_ = [
+        ("plane", C.c_double * 4), ("dompla", (C.c_double * 4) * 4),
+        ("limitmin1", C.c_double * 3), ("limitmin2", C.c_double * 3), ("limitmax1", C.c_double * 3),
+        ("limitmax2", C.c_double * 3), ("limitover1", C.c_double * 3), ("limitover2", C.c_double * 3),
+        ("boxsize1", C.c_double * 3), ("boxsize2", C.c_double * 3),
+        ("axislen", C.c_double), ("dist", C.c_float), ("vertical", C.c_int32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: np.array(getattr(self, k)) if isinstance(getattr(self, k), C.Array) else getattr(self, k)
+                for k, _ in self._fields_}
+
+
+def accinput_arrays(accinputs: list):
+    """SphAccInputDef[] and the rows (float64 [n][7]: time, linx, liny, linz, angx, angy, angz) of
+    XmlCase.accinputs: dicts with code1, code2, globalgravity, timestart, timeend, centre, rows."""
+    arr = (SphAccInputDef * max(1, len(accinputs)))()
+    rows = []
+    n = 0
+    for i, a in enumerate(accinputs):
+        r = np.asarray(a["rows"], np.float64).reshape(-1, 7)
+        arr[i].code1, arr[i].code2 = int(a["code1"]), int(a["code2"])
+        arr[i].globalgravity = int(bool(a["globalgravity"]))
+        arr[i].row0, arr[i].nrows = n, len(r)
+        arr[i].timestart, arr[i].timeend = float(a["timestart"]), float(a["timeend"])
+        for k in range(3):
+            arr[i].centre[k] = float(a["centre"][k])
+        rows.append(r)
+        n += len(r)
+    allrows = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 7)), np.float64)
+    return arr, allrows
+
+
+def damping_array(damping: list):
+    """SphDampingDef[] of XmlCase.damping: dicts with type ("plane", "box", "cylinder"), overlimit,
+    redumax, factorxyz and, per type, plane: limitmin, limitmax (+ dompt [4][2], domzmin, domzmax);
+    box: directions (DAMP_DIRS bits), limitmin_ini / _end, limitmax_ini / _end; cylinder: point1,
+    point2, radmin, radmax."""
+    arr = (SphDampingDef * max(1, len(damping)))()
+    for i, d in enumerate(damping):
+        z = arr[i]
+        z.type = DAMP_TYPES[d["type"]]
+        z.overlimit, z.redumax = float(d["overlimit"]), float(d.get("redumax", 10.0))
+        for k, v in enumerate(d.get("factorxyz", (1.0, 1.0, 1.0))):
+            z.factorxyz[k] = float(v)
+        pts = {"plane": ("limitmin", "limitmax"), "box": ("limitmin_ini", "limitmin_end", "limitmax_ini", "limitmax_end"),
+               "cylinder": ("point1", "point2")}[d["type"]]
+        for j, key in enumerate(pts):
+            for k in range(3):
+                z.pt[j][k] = float(d[key][k])
+        if d["type"] == "plane" and d.get("dompt") is not None:
+            z.usedomain = 1
+            for j in range(4):
+                z.dompt[j][0], z.dompt[j][1] = float(d["dompt"][j][0]), float(d["dompt"][j][1])
+            z.domzmin, z.domzmax = float(d["domzmin"]), float(d["domzmax"])
+        if d["type"] == "box":
+            z.directions = int(d.get("directions", 63))
+        if d["type"] == "cylinder":
+            z.radmin, z.radmax = float(d["radmin"]), float(d["radmax"])
+    return arr
+
+
 def _fill(struct, d: dict):
     for k, v in d.items():
         if k not in dict(struct._fields_):
@@ -520,4 +607,7 @@ def check_struct_sizes() -> dict:
         "SphFloatingState": C.sizeof(SphFloatingState),
         "SphGaugeDef": C.sizeof(SphGaugeDef),
         "SphGaugeRecord": C.sizeof(SphGaugeRecord),
+        "SphAccInputDef": C.sizeof(SphAccInputDef),
+        "SphDampingDef": C.sizeof(SphDampingDef),
+        "SphDampingDerived": C.sizeof(SphDampingDerived),
     }

@@ -36,6 +36,11 @@ from ._abi import (
     GAUGE_RECORD_DTYPE,
     SPH_FLAG_GAUGE_FULL,
     gauge_array,
+    SphAccInputDef,
+    SphDampingDef,
+    SphDampingDerived,
+    accinput_arrays,
+    damping_array,
     SphMotionEvent,
     SphMotionMov,
     SphMotionObj,
@@ -107,6 +112,10 @@ EXPORTED_SYMBOLS = (
     "sph_solver_set_gauges",
     "sph_solver_gauge_records",
     "sph_solver_measure",
+    "sph_solver_set_accinputs",
+    "sph_solver_set_damping",
+    "sph_accinput_velocities",
+    "sph_damping_derive",
 )
 
 
@@ -197,6 +206,11 @@ def load_library(path: str = LIB_PATH):
     L.sph_solver_set_gauges.argtypes = [vp, C.c_uint32, C.POINTER(SphGaugeDef), C.c_uint32]
     L.sph_solver_gauge_records.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     L.sph_solver_measure.argtypes = [vp, vp, C.c_uint32]
+    L.sph_solver_set_accinputs.argtypes = [vp, C.c_uint32, C.POINTER(SphAccInputDef), C.c_uint32,
+                                           C.POINTER(C.c_double)]
+    L.sph_solver_set_damping.argtypes = [vp, C.c_uint32, C.POINTER(SphDampingDef)]
+    L.sph_accinput_velocities.argtypes = [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sph_damping_derive.argtypes = [C.POINTER(SphDampingDef), C.c_uint32, C.POINTER(SphDampingDerived)]
     if L.sph_abi_version() != SPH_ABI_VERSION:
         raise SphError(3, "ABI version mismatch")
     _lib = L
@@ -213,6 +227,25 @@ def case_derive(case_def: dict) -> dict:
     k = SphConstants()
     _check(load_library().sph_case_derive(C.byref(SphCaseDef.from_dict(case_def)), C.byref(k)))
     return k.as_dict()
+
+
+def accinput_velocities(rows) -> np.ndarray:
+    """The velocity rows [n][6] the core integrates from an input's rows [n][7]
+    (JDsAccInput::ComputeVelocity; no GPU needed)."""
+    rows = np.ascontiguousarray(rows, np.float64).reshape(-1, 7)
+    out = np.zeros((len(rows), 6), np.float64)
+    dp = C.POINTER(C.c_double)
+    _check(load_library().sph_accinput_velocities(len(rows), rows.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return out
+
+
+def damping_derive(damping: list, index: int) -> dict:
+    """The geometry the core derives for zone `index` of XmlCase.damping, with the reference's
+    configuration checks (no GPU needed)."""
+    out = SphDampingDerived()
+    arr = damping_array(damping)
+    _check(load_library().sph_damping_derive(C.byref(arr[index]), index, C.byref(out)))
+    return out.as_dict()
 
 
 def case_particles(case) -> HostParticles:
@@ -255,6 +288,11 @@ class SphGpuSingle:
         for kind, key in ((SPH_TTAB_DTFIXED, "dtfixed_table"), (SPH_TTAB_VISCO, "visco_table")):
             if getattr(case, key, None) is not None:
                 self.set_time_table(kind, getattr(case, key))
+        # <special><accinputs> / <damping> (JSph::LoadCaseConfig, JSph.cpp: AccInput, Damping)
+        if getattr(case, "accinputs", None):
+            self.set_accinputs(case.accinputs)
+        if getattr(case, "damping", None):
+            self.set_damping(case.damping)
         if not getattr(case, "has_bodies", False):
             return
         # a restart sets the PART time first: the motion program is advanced to it
@@ -283,6 +321,18 @@ class SphGpuSingle:
                     dp = C.POINTER(C.c_double)
                     _check(L.sph_solver_set_floating_table(self._h, b, kind, len(rows), t.ctypes.data_as(dp),
                                                            v.ctypes.data_as(dp)))
+
+    def set_accinputs(self, accinputs: list) -> None:
+        """Imposed accelerations (XmlCase.accinputs dicts: code1, code2, globalgravity, timestart,
+        timeend, centre, rows [n][7]) of Interaction_Forces; once, before the first step."""
+        arr, rows = accinput_arrays(accinputs)
+        _check(load_library().sph_solver_set_accinputs(self._h, len(accinputs), arr, len(rows),
+                                                        rows.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def set_damping(self, damping: list) -> None:
+        """Damping zones (XmlCase.damping dicts, _abi.damping_array) applied after every step's last
+        update; once, before the first step."""
+        _check(load_library().sph_solver_set_damping(self._h, len(damping), damping_array(damping)))
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -571,6 +621,16 @@ class SphSlabGroup:
         """Restart time of every slab (JSph::InitRun with PartBegin)."""
         for m in self.members:
             m.set_time(time, symplectic_dtpre)
+
+    def set_accinputs(self, accinputs: list) -> None:
+        """Imposed accelerations on every slab (SphGpuSingle.set_accinputs)."""
+        for m in self.members:
+            m.set_accinputs(accinputs)
+
+    def set_damping(self, damping: list) -> None:
+        """Damping zones on every slab (SphGpuSingle.set_damping)."""
+        for m in self.members:
+            m.set_damping(damping)
 
     def set_repartition(self, every: int, bound_weight: float = 0.3, tolerance: float = 0.05) -> None:
         """Re-balance the slabs' column bounds every `every` steps."""

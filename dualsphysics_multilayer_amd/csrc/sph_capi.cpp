@@ -184,6 +184,41 @@ int sph_solver_measure(SphSolver* s, SphGaugeRecord* out, uint32_t n) {
   NOT_MEMBER(s);
   return guard([&] { s->impl->Measure(out, n); });
 }
+int sph_solver_set_accinputs(SphSolver* s, uint32_t n, const SphAccInputDef* defs, uint32_t nrows, const double* rows) {
+  NEED(s && defs && n && (rows || !nrows));
+  return guard([&] { s->impl->SetAccInputs(n, defs, nrows, rows); });
+}
+int sph_solver_set_damping(SphSolver* s, uint32_t n, const SphDampingDef* defs) {
+  NEED(s && defs && n);
+  return guard([&] { s->impl->SetDamping(n, defs); });
+}
+int sph_accinput_velocities(uint32_t nrows, const double* rows, double* out) {
+  NEED(rows && out);
+  return guard([&] { sphx::accinput_velocities(nrows, rows, out); });
+}
+int sph_damping_derive(const SphDampingDef* def, uint32_t index, SphDampingDerived* out) {
+  NEED(def && out);
+  return guard([&] {
+    sphx::DampZoneDev z;
+    sphx::derive_damping(*def, index, z);
+    std::memset(out, 0, sizeof(*out));
+    std::memcpy(out->plane, z.plane, sizeof(z.plane));
+    std::memcpy(out->dompla, z.dompla, sizeof(z.dompla));
+    for (int k = 0; k < 3; k++) {
+      out->limitmin1[k] = z.bmin1[k];
+      out->limitmin2[k] = z.bmin2[k];
+      out->limitmax1[k] = z.bmax1[k];
+      out->limitmax2[k] = z.bmax2[k];
+      out->limitover1[k] = z.bover1[k];
+      out->limitover2[k] = z.bover2[k];
+      out->boxsize1[k] = z.bsize1[k];
+      out->boxsize2[k] = z.bsize2[k];
+    }
+    out->axislen = z.axislen;
+    out->dist = z.dist;
+    out->vertical = z.vertical;
+  });
+}
 int sph_partfloat_write(const char* path, const char* app, uint32_t mkboundfirst, uint32_t nft,
                         const uint16_t* mkbound, const uint32_t* begin, const uint32_t* count, const float* mass,
                         const float* massp, const float* radius, uint32_t nparts, const uint32_t* cpart,

@@ -237,6 +237,24 @@ __device__ inline void wave_max_atomic(DevScalars* sc, int which, float v) {
   const unsigned wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if ((threadIdx.x & 63) == 0 && b) atomicMax(&sc->red[which][wave & (RED_SLOTS - 1)], b);
 }
+// The same reduction (the same bits) for a kernel of 256-thread blocks that lasts only a few
+// microseconds: one atomic per block instead of one per wave, and none when the slot already
+// holds as much (a max only grows, so a stale read skips no larger value).  Every thread of the
+// block must call it.  k_accinput with one atomic per wave, 16,000 on the two 128-B lines of
+// the slots at cfg2, took 57 us instead of 29.
+__device__ __forceinline__ void block_max_atomic(DevScalars* sc, int which, float v) {
+  __shared__ unsigned wmax[4];
+  unsigned b = (v != v) ? 0x7fc00000u : __float_as_uint(fmaxf(v, 0.f));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, off, 64));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = b;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    b = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    unsigned* slot = &sc->red[which][blockIdx.x & (RED_SLOTS - 1)];
+    if (b > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, b);
+  }
+}
 // max that keeps a NaN (fmaxf drops it): per-thread VelMax accumulation, so that a NaN
 // velocity reaches the dt (the reference's DtVariable check, JSphCpu.cpp:1622)
 __device__ __forceinline__ float nanmax(float a, float x) { return (x != x || a != a) ? __builtin_nanf("") : fmaxf(a, x); }

@@ -17,6 +17,7 @@
 
 #include "../../include/sphcore.h"
 #include "sph_comm.hpp"
+#include "sph_forcing.hpp"
 #include "sph_gauge.hpp"
 #include "sph_kernels.hpp"
 
@@ -30,6 +31,10 @@ struct SphError : std::runtime_error {
 void check_hip(hipError_t e, const char* what);
 void test_hook_notice(const char* name);
 void derive_constants(const SphCaseDef& c, SphConstants& k);
+// Imposed accelerations / damping zones: the integrated velocity rows [nrows][6] of an input's
+// rows [nrows][7], and the derived geometry of zone i of a list (sph_solver.cpp; no device).
+void accinput_velocities(unsigned nrows, const double* rows, double* out);
+void derive_damping(const SphDampingDef& d, unsigned i, DampZoneDev& z);
 // Ghost columns per slab face (scelldiv, +1 with mDBC).
 int ghost_width(const SphConstants& c);
 // Narrowest slab between two neighbours (2 x ghost width).
@@ -144,6 +149,9 @@ class SphGpuSingle {
   unsigned GaugeRecords(SphGaugeRecord* out, unsigned cap);
   // Every gauge evaluated now on the current state; schedules and records untouched.
   void Measure(SphGaugeRecord* out, unsigned n);
+  // Imposed accelerations and damping zones (sph_forcing.hip), configured once before the first step.
+  void SetAccInputs(unsigned n, const SphAccInputDef* defs, unsigned nrows, const double* rows);
+  void SetDamping(unsigned n, const SphDampingDef* defs);
 
   SphConstants C{};
   KConst K{};
@@ -173,6 +181,7 @@ class SphGpuSingle {
   void RunMotion();                 // JSphCpu::RunMotion after ComputeStep (JSphCpuSingle.cpp:1096)
   void RunFloating(bool predictor); // JSphCpuSingle::RunFloating
   void RunGauges();                 // JSphCpuSingle::RunGaugeSystem(TimeStep + stepdt) (JSphCpuSingle.cpp:1095)
+  void RunDamping();                // JSphCpu::RunDamping(dt) on the new velocity (JSphCpuSingle.cpp:683,717)
   void TimedBegin(int phase);
   void TimedEnd(int phase);
 
@@ -280,6 +289,14 @@ class SphGpuSingle {
   unsigned casenpb_ = 0;         // CaseNpb: first floating idp
   bool stepped_ = false;         // a step was issued (bodies are configured before it)
   GaugeSet gauges_;              // the gauges (ng = 0: none; nothing is allocated or launched)
+  // imposed accelerations (acc_.n = 0: none, nothing launched): the inputs, their table rows
+  // (ACC_ROWW doubles each), JLinearValue lookup states and the values of the last interaction
+  AccInSet acc_{};
+  double* accrows_ = nullptr;
+  AccState* accstate_ = nullptr;
+  AccVals* accvals_ = nullptr;
+  DampZoneDev* dampzones_ = nullptr;  // damping zones in list order (ndamp_ = 0: none, nothing launched)
+  int ndamp_ = 0;
   // turns measurement mode: the dt maxima of the next DtVariable are folded at the end of the
   // interaction's turn (fold_turn_: its clear flag, -1 none), so that k_fold runs alone on the
   // GPU as on a rank's own; folded_ready_: DtVariable finds them folded

@@ -364,8 +364,17 @@ class XmlCase:
                     continue
                 if ch.tag == "gauges":
                     continue  # read below, once TimeMax / TimeOut and the blocks are known
+                if ch.tag in ("accinputs", "damping"):
+                    if self.rheology == 2 and _active(ch):
+                        raise CaseError(f"<special><{ch.tag}> with NN multiphase is not supported by this core.")
+                    continue  # read below, once the blocks are known
                 raise CaseError(f"<special><{ch.tag}> is not supported by this core.")
         self._load_blocks(_node(ex, "particles"))
+        # <special><accinputs> / <damping> (JSph::LoadCaseConfig: JDsAccInput, JDsDamping)
+        anode = sp.find("accinputs") if sp is not None else None
+        self.accinputs = self._load_accinputs(anode) if anode is not None and _active(anode) else []
+        dnode = sp.find("damping") if sp is not None else None
+        self.damping = self._load_damping(dnode) if dnode is not None and _active(dnode) else []
         if self.rheology == 2:  # JSph::InitMultiPhase (JSph.cpp:3137-3215 of the v5.0 solver)
             node = sp.find("nnphases") if sp is not None else None
             if node is not None:
@@ -659,6 +668,192 @@ class XmlCase:
         self.floatings = [dict(b["floating"], idbegin=b["begin"], count=b["count"], mkbound=b["mktype"])
                           for b in bytype["floating"]]
 
+    # -- JDsAccInput::ReadXml + Init (JDsAccInput.cpp:168-233, 293-328) -------------------------
+    def _load_accinputs(self, lis) -> list:
+        """<special><accinputs> as dicts: code1, code2 (TypeAndValue range of the selected
+        blocks), bound, mk1, mk2, globalgravity, timestart, timeend, centre, rows [n][7] (time,
+        linx, liny, linz, angx, angy, angz) and file (the <acctimesfile>, or None).  An mk list
+        gives one dict per run of consecutive mk."""
+        out = []
+
+        def exist_mk(bound, mk):
+            return any(a["bound"] == bound and a["mk1"] <= mk <= a["mk2"] for a in out)
+
+        for ele in lis.findall("accinput"):
+            if not _active(ele):
+                continue
+            for old in ("mkfluid", "datafile"):
+                if ele.find(old) is not None:
+                    raise CaseError(f"Element <{old}> is invalid for current version. Update the XML file.")
+            for ch in ele:
+                if not ch.tag.startswith("_") and ch.tag not in ("time", "acccentre", "globalgravity", "acctimes",
+                                                                 "acctimesfile"):
+                    raise CaseError(f"Element <{ch.tag}> is invalid in <accinput>.")
+            if ele.find("acctimes") is not None and ele.find("acctimesfile") is not None:
+                raise CaseError("Only <acctimes> or <acctimesfile> is valid but not both.")
+            if ele.get("mkbound") is not None and ele.get("mkfluid") is not None:
+                raise CaseError("Only mkbound or mkfluid values is valid but not both.")
+            tnode = ele.find("time")
+            tini = float(tnode.get("start", 0)) if tnode is not None else 0.0
+            tend = float(tnode.get("end", DBL_MAX)) if tnode is not None else DBL_MAX
+            cen = _node(ele, "acccentre")
+            centre = [float(np.float32(_attr_double(cen, ax, "acccentre"))) for ax in "xyz"]  # tfloat3
+            genabled = _elem_bool(ele, "globalgravity")
+            bound = ele.get("mkbound") is not None
+            name = "mkbound" if bound else "mkfluid"
+            strmk = (ele.get(name) or "").strip()
+            # rows of the table: JLinearValue(6), missing attributes read as 0
+            file = None
+            if ele.find("acctimes") is not None:
+                rows = [[float(tv.get(k, 0)) if k != "time" else _attr_double(tv, "time", "timevalue")
+                         for k in ("time", "linx", "liny", "linz", "angx", "angy", "angz")]
+                        for tv in ele.find("acctimes").findall("timevalue")]
+                rows = np.array(rows, np.float64).reshape(-1, 7)
+            else:
+                fe = _node(ele, "acctimesfile")
+                file = fe.get("value")
+                if file is None:
+                    raise CaseError("The attribute 'value' of 'acctimesfile' is missing.")
+                rows = _read_datafile(os.path.join(self._dircase, file), "<acctimesfile>", 6)
+            if len(rows) < 2:  # ComputeVelocity (JDsAccInput.cpp:271)
+                raise CaseError("Cannot be less than two registers in variable acceleration data.")
+            # the mk values: one, or a JRangeFilter list ("1,3-5", "2-8:2") split into consecutive runs
+            if strmk.isdigit():
+                vmk = [int(strmk)]
+            else:
+                vals = set()
+                for tx in strmk.split(","):
+                    tx = tx.strip()
+                    if not tx or tx.startswith("-"):
+                        continue
+                    a, _, b = tx.partition("-")
+                    b, _, st = b.partition(":")
+                    try:
+                        if not b:
+                            vals.add(int(a))
+                        else:
+                            vals.update(range(int(a), int(b) + 1, int(st) if st else 1))
+                    except ValueError:
+                        raise CaseError(f"The {name} is invalid.") from None
+                vmk = sorted(vals)
+                if not vmk:
+                    raise CaseError(f"The {name} is invalid.")
+            for mk in vmk:
+                if exist_mk(bound, mk):
+                    raise CaseError(f"An input already exists for the same {name}={mk}.")
+            runs = [[vmk[0], vmk[0]]]
+            for v in vmk[1:]:
+                if runs[-1][1] + 1 == v:
+                    runs[-1][1] = v
+                else:
+                    runs.append([v, v])
+            for mk1, mk2 in runs:
+                out.append(dict(bound=bound, mk1=mk1, mk2=mk2, globalgravity=genabled, timestart=tini, timeend=tend,
+                                centre=centre, rows=rows, file=file))
+        # Init: the mk exist (floating bodies only for mkbound); codes of the first / last block
+        for a in out:
+            codes = []
+            for mk in range(a["mk1"], a["mk2"] + 1):
+                if a["bound"]:
+                    blk = [b for b in self.blocks if b["type"] != "fluid" and b["mktype"] == mk]
+                    if not blk:
+                        raise CaseError(f"The MkBound {mk} with imposed acceleration is not present in the simulation.")
+                    if blk[0]["type"] != "floating":
+                        raise CaseError(f"The MkBound {mk} with imposed acceleration is not floating body.")
+                else:
+                    blk = [b for b in self.blocks if b["type"] == "fluid" and b["mktype"] == mk]
+                    if not blk:
+                        raise CaseError(f"The MkFluid {mk} with imposed acceleration is not present in the simulation.")
+                codes.append(int(blk[0]["code"]))
+            a["code1"], a["code2"] = codes[0], codes[-1]
+        return out
+
+    # -- JDsDamping::ReadXml (JDsDamping.cpp:667-683) and the zones' ReadXml ---------------------
+    def _load_damping(self, lis) -> list:
+        """<special><damping> as dicts in list order (the fields of _abi.damping_array): type
+        "plane" / "box" / "cylinder", overlimit, redumax, factorxyz and the type's raw values."""
+        out = []
+
+        def f32(v):
+            return float(np.float32(v))
+
+        def p3(node, name):
+            e = _node(node, name)
+            return [_attr_double(e, ax, name) for ax in "xyz"]
+
+        def check_names(ele, names):
+            for ch in ele:
+                if not ch.tag.startswith("_") and ch.tag not in names:
+                    raise CaseError(f"Element <{ch.tag}> is invalid in <{ele.tag}>.")
+
+        for ele in lis:
+            cmd = ele.tag
+            if not isinstance(cmd, str) or not cmd or cmd[0] == "_" or not _active(ele):
+                continue
+            idx = len(out)
+            err = f"Error in configuration of damping {idx}."
+            if cmd not in ("dampingzone", "dampingbox", "dampingcylinder"):
+                raise CaseError(f"Element <{cmd}> is invalid in <damping>.")
+            common = {"overlimit", "redumax", "factorxyz"}
+            fx = ele.find("factorxyz")
+            z = dict(overlimit=f32(_elem_double(ele, "overlimit")), redumax=f32(_elem_double(ele, "redumax", True, 10.0)),
+                     factorxyz=[f32(fx.get(ax, 1)) if fx is not None else 1.0 for ax in "xyz"])
+            if cmd == "dampingzone":
+                check_names(ele, common | {"limitmin", "limitmax", "domain"})
+                z.update(type="plane", limitmin=p3(ele, "limitmin"), limitmax=p3(ele, "limitmax"), dompt=None)
+                dom = ele.find("domain")
+                if dom is not None:
+                    z["domzmin"], z["domzmax"] = _attr_double(dom, "zmin", "domain"), _attr_double(dom, "zmax", "domain")
+                    z["dompt"] = [[_attr_double(_node(dom, f"point{k}"), ax, f"point{k}") for ax in "xy"]
+                                  for k in (1, 2, 3, 4)]
+            elif cmd == "dampingbox":
+                check_names(ele, common | {"directions", "limitmin", "limitmax"})
+                z.update(type="box", directions=self._damping_directions(ele))
+                emin, emax = _node(ele, "limitmin"), _node(ele, "limitmax")
+                z.update(limitmin_ini=p3(emin, "pointini"), limitmin_end=p3(emin, "pointend"),
+                         limitmax_ini=p3(emax, "pointini"), limitmax_end=p3(emax, "pointend"))
+                le = lambda a, b: all(x <= y for x, y in zip(a, b))  # noqa: E731
+                if not le(z["limitmin_ini"], z["limitmin_end"]):
+                    raise CaseError(err + " Begin of LimitMin is higher than end of LimitMin.")
+                if not le(z["limitmax_ini"], z["limitmax_end"]):
+                    raise CaseError(err + " Begin of LimitMax is higher than end of LimitMax.")
+                if not le(z["limitmax_ini"], z["limitmin_ini"]) or not le(z["limitmin_end"], z["limitmax_end"]):
+                    raise CaseError(err + " LimitMin box is not inside of LimitMax box.")
+                if z["overlimit"] < 0:
+                    raise CaseError(err + " OverLimit must be higher than 1.")
+            else:
+                check_names(ele, common | {"point1", "point2", "limitmin", "limitmax"})
+                z.update(type="cylinder", point1=p3(ele, "point1"), point2=p3(ele, "point2"),
+                         radmin=_attr_double(_node(ele, "limitmin"), "radius", "limitmin"),
+                         radmax=_attr_double(_node(ele, "limitmax"), "radius", "limitmax"))
+                if z["radmin"] > z["radmax"]:
+                    raise CaseError(err + " LimitMin radius is higher than LimitMax radius.")
+            out.append(z)
+        return out
+
+    @staticmethod
+    def _damping_directions(ele) -> int:
+        """JDsDampingOp_Box::ReadXmlDirections (JDsDamping.cpp:313-340): "top,left", "all -back", ..."""
+        from ._abi import DAMP_DIRS
+
+        e = ele.find("directions")
+        dirs = ((e.get("value") if e is not None else "") or "").replace(",", " ").lower().split()
+        if not dirs:
+            return DAMP_DIRS["all"]
+        ret = 0
+        for v in dirs:
+            add = True
+            if v[0] == "+":
+                v = v[1:]
+            if v[:1] == "-":
+                v, add = v[1:], False
+            if v not in DAMP_DIRS:
+                raise CaseError("Error reading the element 'directions'. Some value is invalid.")
+            ret = (ret | DAMP_DIRS[v]) if add else (ret & (DAMP_DIRS["all"] ^ DAMP_DIRS[v]))
+        if ret == 0:
+            raise CaseError("Error reading the element 'directions'. At least one direction must be confirured.")
+        return ret
+
     # -- JSph::InitMultiPhase (JSph.cpp:3137-3215, v5.0 NN solver) -----------------------------
     def _load_phases(self, node):
         known = {"rhop", "csound", "gamma", "visco", "tau_yield", "tau_max", "Bi_multi", "HBP_n", "HBP_m",
@@ -701,9 +896,11 @@ class XmlCase:
     @property
     def explicit_codes(self) -> bool:
         """NN multiphase: the core takes the fluid block codes (the phase of each particle).
-        A force gauge on a block other than the first fixed one needs the block codes too."""
+        A force gauge on a block other than the first fixed one needs the block codes too, and
+        so do imposed accelerations: they select particles by block code, and without the codes
+        every fluid particle is the first block's."""
         return self.rheology == 2 or any(g["type"] == "force" and g["code"] != CODE_TYPE_FIXED
-                                         for g in getattr(self, "gauges", ()))
+                                         for g in getattr(self, "gauges", ())) or bool(getattr(self, "accinputs", ()))
 
     # -- JGaugeSystem::ReadXml (JDsGaugeSystem.cpp:186-275) --------------------------------------
     def _load_gauges(self, node) -> list:

@@ -56,6 +56,9 @@
  *   sph_solver_set_gauges ...... JGaugeSystem (JDsGaugeSystem.cpp, JDsGaugeItem.cpp): velocity,
  *     sph_solver_gauge_records   SWL, MaxZ and force gauges evaluated and recorded on the device
  *     sph_solver_measure         after every step's update (RunGaugeSystem, JSphCpuSingle.cpp:1095)
+ *   sph_solver_set_accinputs ... JDsAccInput::RunCpu in PreInteractionVars_Forces (JSphCpu.cpp:444)
+ *   sph_solver_set_damping ..... JSphCpu::RunDamping at the end of ComputeStep_Ver / _Sym
+ *                                (JSphCpuSingle.cpp:683,717; JDsDamping.cpp)
  */
 #ifndef SPHCORE_H
 #define SPHCORE_H
@@ -67,7 +70,7 @@
 extern "C" {
 #endif
 
-#define SPH_ABI_VERSION 14
+#define SPH_ABI_VERSION 15
 
 typedef enum {
   SPH_OK = 0,
@@ -659,6 +662,73 @@ int sph_solver_gauge_records(SphSolver* s, SphGaugeRecord* out, uint32_t cap, ui
 /* Evaluate every gauge now, on the current state (synchronises): out[n], in list order.  The
  * schedules are ignored and left unchanged, nothing is recorded. */
 int sph_solver_measure(SphSolver* s, SphGaugeRecord* out, uint32_t n);
+
+/* ---- imposed accelerations (<special><accinputs>, JDsAccInput): a time-dependent linear and
+ * angular acceleration on the fluid blocks or floating bodies whose particle code (type |
+ * block index, JSphMk) lies in [code1, code2].  Part of Interaction_Forces, where the reference
+ * calls JDsAccInput::RunCpu (JSphCpu.cpp:444): while timestart <= TimeStep <= timeend the
+ * acceleration of every selected particle gets acclin (- Gravity unless globalgravity)
+ * + accang x dc + velang x (velang x dc) + the Coriolis term of JDsAccInput.cpp:383-385, with
+ * dc = pos - centre; AceMax of the dt control covers the result.  The six values (linx, liny,
+ * linz, angx, angy, angz) come from the input's rows (7 doubles each: time and the values;
+ * rows [row0, row0 + nrows) of `rows`), interpolated on the device as JLinearValue does; the
+ * velocities are their running sum v += a dt from zero at the first row (ComputeVelocity,
+ * JDsAccInput.cpp:238-274), integrated by the core.  Once, before the first step (a restart's
+ * sph_solver_set_time before or after it); single phase only; on slabs on every rank. */
+#define SPH_MAX_ACCINPUTS 16
+typedef struct SphAccInputDef {
+  uint32_t code1, code2;        /* CodeSel1..CodeSel2: fluid or floating blocks    */
+  int32_t globalgravity;        /* 0: Gravity is subtracted                        */
+  uint32_t row0, nrows;         /* its rows of the table (nrows >= 2)              */
+  uint32_t pad;
+  double timestart, timeend;    /* <time start end>                                */
+  double centre[3];             /* <acccentre> (held as float, as the reference's) */
+} SphAccInputDef;
+int sph_solver_set_accinputs(SphSolver* s, uint32_t n, const SphAccInputDef* defs, uint32_t nrows, const double* rows);
+
+/* ---- damping zones (<special><damping>, JDsDamping): after the last update of every step
+ * (JSphCpuSingle.cpp:683,717; not after the Symplectic predictor) the new velocity of every
+ * normal fluid particle inside a zone is multiplied per axis by max(0, 1 - dt fdis^2 redumax
+ * factorxyz), zone after zone in list order.  The values are the XML's; the core derives the
+ * planes, box limits and distances as JDsDampingOp_*::ReadXml do.
+ *   PLANE     <dampingzone>: pt[0] limitmin, pt[1] limitmax; usedomain: dompt[4] (x, y) of
+ *             <domain> point1..4 and domzmin / domzmax
+ *   BOX       <dampingbox>: pt[0..1] limitmin pointini / pointend, pt[2..3] limitmax pointini /
+ *             pointend, directions (SPH_DAMPDIR_* bits)
+ *   CYLINDER  <dampingcylinder>: pt[0] point1, pt[1] point2, radmin / radmax the limit radii
+ * Once, before the first step; single phase only; on slabs on every rank. */
+#define SPH_MAX_DAMPINGS 16
+enum { SPH_DAMP_PLANE = 0, SPH_DAMP_BOX = 1, SPH_DAMP_CYLINDER = 2 };
+enum { SPH_DAMPDIR_TOP = 1, SPH_DAMPDIR_BOTTOM = 2, SPH_DAMPDIR_LEFT = 4, SPH_DAMPDIR_RIGHT = 8,
+       SPH_DAMPDIR_FRONT = 16, SPH_DAMPDIR_BACK = 32, SPH_DAMPDIR_ALL = 63 };
+typedef struct SphDampingDef {
+  int32_t type;                 /* SPH_DAMP_*                                      */
+  int32_t usedomain;            /* PLANE: <domain> given                           */
+  uint32_t directions;          /* BOX: SPH_DAMPDIR_* bits                         */
+  float overlimit, redumax;
+  float factorxyz[3];
+  double pt[4][3];
+  double dompt[4][2];
+  double domzmin, domzmax;
+  double radmin, radmax;
+} SphDampingDef;
+int sph_solver_set_damping(SphSolver* s, uint32_t n, const SphDampingDef* defs);
+/* Diagnostic helpers, not needed to run a case: what the core derives on the host for the
+ * device passes (no GPU needed), so that a binding or a test can inspect it.  The velocity rows
+ * out[nrows][6] of an input's rows[nrows][7], and the geometry of zone `index` of a list
+ * (Plane, Dist, DomPla0-3; the box's LimitMin/Max/Over and BoxSize after the directions; the
+ * cylinder's Dist, vertical shortcut and axis length), with the configuration checks. */
+typedef struct SphDampingDerived {
+  double plane[4];
+  double dompla[4][4];
+  double limitmin1[3], limitmin2[3], limitmax1[3], limitmax2[3];
+  double limitover1[3], limitover2[3], boxsize1[3], boxsize2[3];
+  double axislen;
+  float dist;
+  int32_t vertical;
+} SphDampingDerived;
+int sph_accinput_velocities(uint32_t nrows, const double* rows, double* out);
+int sph_damping_derive(const SphDampingDef* def, uint32_t index, SphDampingDerived* out);
 
 #ifdef __cplusplus
 }
