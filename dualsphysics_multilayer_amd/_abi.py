@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-SPH_ABI_VERSION = 15
+SPH_ABI_VERSION = 16
 
 SPH_STATUS = {
     0: "SPH_OK",
@@ -32,7 +32,9 @@ _CASEDEF_DEFAULTS = {"tboundary": SPH_BOUND_DBC, "slipmode": SPH_SLIP_VEL0, "mdb
                      "nphases": 0, "relaxation_dt": 0.2, "shift_mode": SPH_SHIFT_NONE, "mdbc_corrector": 0,
                      "shift_coef": -2.0, "shift_tfs": 0.0, "phases": (),
                      "data2d": 0, "pad2d": 0, "data2d_posy": 0.0, "dtallparticles": 0, "symmetry": 0,
-                     "dtfixed": 0.0}
+                     "dtfixed": 0.0,
+                     "peri_active": 0, "pad_peri": 0, "peri_xinc": (0.0, 0.0, 0.0), "peri_yinc": (0.0, 0.0, 0.0),
+                     "peri_zinc": (0.0, 0.0, 0.0)}
 SPH_TTAB_DTFIXED, SPH_TTAB_VISCO = 0, 1
 
 
@@ -101,6 +103,12 @@ class SphCaseDef(C.Structure):
         ("dtallparticles", C.c_int32),
         ("symmetry", C.c_int32),
         ("dtfixed", C.c_double),
+        # periodic boundaries: PeriActive bits (1 X, 2 Y, 4 Z) and the XML's offsets
+        ("peri_active", C.c_int32),
+        ("pad_peri", C.c_int32),
+        ("peri_xinc", C.c_double * 3),
+        ("peri_yinc", C.c_double * 3),
+        ("peri_zinc", C.c_double * 3),
     ]
 
     @classmethod
@@ -196,6 +204,13 @@ class SphConstants(C.Structure):
         ("dtallparticles", C.c_int32),
         ("symmetry", C.c_int32),
         ("dtfixed", C.c_double),
+        ("peri_active", C.c_int32),
+        ("pad5", C.c_int32),
+        ("peri_xinc", C.c_double * 3),
+        ("peri_yinc", C.c_double * 3),
+        ("peri_zinc", C.c_double * 3),
+        ("map_posmin", C.c_double * 3),
+        ("map_posmax", C.c_double * 3),
     ]
 
     def as_dict(self) -> dict:
@@ -223,6 +238,8 @@ class SphRunStats(C.Structure):
         ("viscdtmax", C.c_float),
         ("viscetadtmax", C.c_float),
         ("fused_updates", C.c_uint64),
+        ("npbper", C.c_uint32),
+        ("npfper", C.c_uint32),
     ]
 
     def as_dict(self) -> dict:
@@ -400,6 +417,7 @@ class SphFloatingState(C.Structure):
 SPH_GAUGE_VEL, SPH_GAUGE_SWL, SPH_GAUGE_MAXZ, SPH_GAUGE_FORCE = 0, 1, 2, 3
 GAUGE_TYPES = {"velocity": SPH_GAUGE_VEL, "swl": SPH_GAUGE_SWL, "maxz": SPH_GAUGE_MAXZ, "force": SPH_GAUGE_FORCE}
 SPH_FLAG_GAUGE_FULL = 64
+SPH_FLAG_PERIODIC_FULL = 128
 
 
 class SphGaugeDef(C.Structure):

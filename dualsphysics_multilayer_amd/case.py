@@ -257,6 +257,11 @@ class DamBreakCase:
             dtfixed=float(getattr(self, "dtfixed", 0.0)),
             symmetry=int(bool(getattr(self, "symmetry", False))),
             mdbc_corrector=int(getattr(self, "mdbc_corrector", 0)) if self.tboundary == 2 else 0,
+            # periodic boundaries (PeriodicChannelCase; any case object may carry them)
+            peri_active=int(getattr(self, "peri_active", 0)),
+            peri_xinc=tuple(getattr(self, "peri_xinc", (0.0, 0.0, 0.0))),
+            peri_yinc=tuple(getattr(self, "peri_yinc", (0.0, 0.0, 0.0))),
+            peri_zinc=tuple(getattr(self, "peri_zinc", (0.0, 0.0, 0.0))),
         )
 
 
@@ -626,3 +631,168 @@ class WetDambreakNNCase:
 def wetdambreak_nn_np(dp: float, width: float = 0.64, scale: float = 1.0) -> int:
     """Particle count of the NN wet dam break (lattice sizes only)."""
     return WetDambreakNNCase(dp, width=width, scale=scale).np
+
+
+@dataclass
+class PeriodicChannelCase:
+    """A layer of fluid over a floor in a box with periodic boundaries (JSph.cpp:718-730), written
+    out as ``Case<name>.xml`` + ``.bi4`` for any solver that loads DualSPHysics cases.
+
+    Lattice (i, j, k) dp with i in [0, nx), so that the real map [-dp/2, (nx - 1/2) dp] has the
+    period nx dp (a periodic axis gets the border Dp/2, JPartsLoad4.cpp:339-347); likewise j in
+    [0, ny) when Y is periodic.  Floor k = 0; with `ywalls` the walls j = 0 and j = ny up to
+    k = nz (Y not periodic); fluid k in [1, depth] between them, hydrostatic, moving with
+    `vel0`.  `data2d`: the plane y = 0 only.  `peri`: the periodic <parameter> keys and their
+    values, in XML order (e.g. {"XPeriodicIncY": 0.06, "YPeriodicIncZ": 0})."""
+
+    dp: float
+    nx: int
+    ny: int
+    nz: int
+    depth: int
+    peri: dict
+    vel0: tuple = (0.0, 0.0, 0.0)
+    ywalls: bool = False
+    data2d: bool = False
+    step_algorithm: int = STEP_VERLET
+    tdensity: int = DDT_DDT2
+    ddtvalue: float = 0.1
+    visco: float = 0.1
+    viscoboundfactor: float = 1.0
+    cflnumber: float = 0.2
+    verlet_steps: int = 40
+    coefdtmin: float = 0.05
+    rhopoutmin: float = 700.0
+    rhopoutmax: float = 1300.0
+    cellmode: int = CELLMODE_FULL
+    celldomfixed: bool = False
+    gravity: tuple = (0.0, 0.0, -9.81)
+    rhop0: float = 1000.0
+    gamma: float = 7.0
+    coefsound: float = 20.0
+    coefh: float = 1.0
+    kernel: int = 2
+    tboundary: int = 1
+    slipmode: int = 1
+    mdbc_threshold: float = 0.0
+    tvisco: int = 1
+    shift_mode: int = 0
+    shift_coef: float = -2.0
+    shift_tfs: float = 0.0
+    timemax: float = 1.0
+    timeout: float = 0.01
+
+    def __post_init__(self) -> None:
+        dp = self.dp
+        axes, incs = [False] * 3, [[0.0] * 3 for _ in range(3)]
+        for key, val in self.peri.items():  # JSph.cpp:718-730
+            if key in ("XYPeriodic", "XZPeriodic", "YZPeriodic"):
+                axes = ["X" in key[:2], "Y" in key[:2], "Z" in key[:2]]
+                incs = [[0.0] * 3 for _ in range(3)]
+            else:
+                ax, comp = "XYZ".index(key[0]), "XYZ".index(key[-1])
+                if key != "%sPeriodicInc%s" % (key[0], key[-1]) or ax == comp:
+                    raise ValueError("unknown periodic key " + key)
+                axes[ax] = True
+                incs[ax][comp] = float(val)
+        self.peri_active = int(axes[0]) | int(axes[1]) << 1 | int(axes[2]) << 2
+        self.peri_xinc, self.peri_yinc, self.peri_zinc = (tuple(v) for v in incs)
+        if self.data2d and axes[1]:
+            raise ValueError("Cannot use periodic conditions in Y with 2D simulations")
+        if self.ywalls and (axes[1] or self.data2d):
+            raise ValueError("y walls need a 3-D case that is not periodic in Y")
+        js = np.arange(1) if self.data2d else np.arange(self.ny + 1 if self.ywalls else self.ny)
+        k, j, i = np.meshgrid(np.arange(self.nz + 1), js, np.arange(self.nx), indexing="ij")
+        wall = (k == 0) | (self.ywalls & ((j == 0) | (j == self.ny)))
+        fj = js[1:-1] if self.ywalls else js
+        fk, fjj, fi = np.meshgrid(np.arange(1, self.depth + 1), fj, np.arange(self.nx), indexing="ij")
+        ii = np.concatenate([i[wall], fi.ravel()]).astype(np.float64)
+        jj = np.concatenate([j[wall], fjj.ravel()]).astype(np.float64)
+        kk = np.concatenate([k[wall], fk.ravel()]).astype(np.float64)
+        self.pos = np.stack([ii * dp, jj * dp, kk * dp], axis=1)
+        self.npb = int(wall.sum())
+        self.np = int(self.pos.shape[0])
+        self.idp = np.arange(self.np, dtype=np.uint32)
+        self.vel = np.zeros((self.np, 3), dtype=np.float32)
+        self.vel[self.npb:] = np.asarray(self.vel0, np.float32)
+        g, rho0, gamma = -self.gravity[2], self.rhop0, self.gamma
+        hswl = self.depth * dp
+        cs0 = self.coefsound * math.sqrt(g * hswl)
+        self._b = cs0 * cs0 * rho0 / gamma
+        dim = 2.0 if self.data2d else 3.0
+        self._h = self.coefh * math.sqrt(dim * dp * dp)
+        self._mass = rho0 * dp ** int(dim)
+        rhop = np.full(self.np, np.float32(rho0), np.float32)
+        z = self.pos[self.npb:, 2]
+        rhop[self.npb:] = (rho0 * np.power(1.0 + rho0 * g * (hswl - z) / self._b, 1.0 / gamma)).astype(np.float32)
+        self.rhop = rhop
+
+    h = DamBreakCase.h
+    cteb = DamBreakCase.cteb
+    mass = DamBreakCase.mass
+    code = DamBreakCase.code
+    nf = DamBreakCase.nf
+    case_def = DamBreakCase.case_def
+
+    @property
+    def boundnormal(self):
+        return None
+
+    def map_limits(self) -> tuple[np.ndarray, np.ndarray]:
+        """MapRealPosMin/Max: border Dp/2 on a periodic axis and no <simulationdomain> there
+        (JSph.cpp:1382-1384), else h BORDER_MAP and posmax z "default + 50%"."""
+        border = float(np.float32(self.h)) * BORDER_MAP
+        dpx = float("%.10g" % self.dp)
+        bor = np.array([dpx / 2.0 if (self.peri_active >> a) & 1 else border for a in range(3)])
+        rmin, rmax = self.pos.min(axis=0) - bor, self.pos.max(axis=0) + bor
+        dmax = rmax + (rmax - rmin) * np.array([0.0, 0.0, 0.5])
+        for a in range(3):
+            if (self.peri_active >> a) & 1:
+                dmax[a] = rmax[a]
+        return rmin, dmax
+
+    def xml(self, app: str = "dualsphysics_multilayer_amd") -> str:
+        g = self.gravity
+        par = [("StepAlgorithm", self.step_algorithm), ("VerletSteps", self.verlet_steps), ("Kernel", self.kernel),
+               ("ViscoTreatment", 1), ("Visco", "%.10g" % self.visco), ("ViscoBoundFactor", "%.10g" % self.viscoboundfactor),
+               ("DensityDT", self.tdensity), ("DensityDTvalue", "%.10g" % self.ddtvalue), ("Shifting", 0),
+               ("RigidAlgorithm", 1), ("CoefDtMin", "%.10g" % self.coefdtmin), ("DtIni", 0), ("DtMin", 0),
+               ("TimeMax", "%.10g" % self.timemax), ("TimeOut", "%.10g" % self.timeout), ("PartsOutMax", 1),
+               ("RhopOutMin", "%.10g" % self.rhopoutmin), ("RhopOutMax", "%.10g" % self.rhopoutmax)]
+        par += [(k, "%.10g" % float(v)) for k, v in self.peri.items()]
+        lines = ['<?xml version="1.0" encoding="UTF-8" ?>', '<case app="%s">' % app, "<execution>", "<constants>",
+                 '<data2d value="%s"/>' % ("true" if self.data2d else "false")]
+        if self.data2d:
+            lines.append('<data2dposy value="0"/>')
+        lines += ['<gravity x="%.10g" y="%.10g" z="%.10g"/>' % tuple(g), '<cflnumber value="%.10g"/>' % self.cflnumber,
+                  '<gamma value="%.10g"/>' % self.gamma, '<rhop0 value="%.10g"/>' % self.rhop0,
+                  '<dp value="%.10g"/>' % self.dp, '<h value="%.10E"/>' % self._h, '<b value="%.10E"/>' % self._b,
+                  '<massbound value="%.10E"/>' % self._mass, '<massfluid value="%.10E"/>' % self._mass, "</constants>",
+                  '<particles np="%d" nb="%d" nbf="%d" mkboundfirst="10" mkfluidfirst="0">' % (self.np, self.npb, self.npb),
+                  '<fixed mkbound="0" mk="10" begin="0" count="%d"/>' % self.npb,
+                  '<fluid mkfluid="0" mk="0" begin="%d" count="%d"/>' % (self.npb, self.np - self.npb), "</particles>",
+                  "<parameters>"]
+        lines += ['<parameter key="%s" value="%s"/>' % kv for kv in par]
+        lines += ['<simulationdomain><posmin x="default" y="default" z="default"/>'
+                  '<posmax x="default" y="default" z="default + 50%"/></simulationdomain>',
+                  "</parameters>", "</execution>", "</case>", ""]
+        return "\n".join(lines)
+
+    def write(self, dirname: str, name: str = "CasePeriodic") -> str:
+        """Case<name>.xml and .bi4 (the case file: PART 0 without map limits, PeriMode unknown, as
+        GenCase writes it) into dirname; returns the case path without extension."""
+        import os
+
+        from .core import write_part
+
+        path = os.path.join(dirname, name)
+        with open(path + ".xml", "w") as f:
+            f.write(self.xml())
+        hdr = dict(app_name="dualsphysics_multilayer_amd", case_name=name, cpart=0, npok=self.np, nout=0, step=0,
+                   timestep=0.0, case_np=self.np, case_nfixed=self.npb, case_nfluid=self.np - self.npb,
+                   dp=float("%.10g" % self.dp), h=self.h, b=self.cteb, rhop0=self.rhop0, gamma=self.gamma,
+                   massbound=self.mass, massfluid=self.mass, case_posmin=self.pos.min(axis=0).tolist(),
+                   case_posmax=self.pos.max(axis=0).tolist(), data2d=int(self.data2d), data2d_posy=0.0,
+                   peri_mode=96, pos_double=1)
+        write_part(path + ".bi4", hdr, dict(idp=self.idp, pos=self.pos, vel=self.vel, rhop=self.rhop))
+        return path

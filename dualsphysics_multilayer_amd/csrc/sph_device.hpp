@@ -22,7 +22,7 @@ namespace sphx {
 
 typedef uint16_t typecode;
 
-constexpr typecode CODE_MASKSPECIAL = 0xe000, CODE_OUTIGNORE = 0x4000, CODE_OUTMOVE = 0x6000,
+constexpr typecode CODE_MASKSPECIAL = 0xe000, CODE_PERIODIC = 0x2000, CODE_OUTIGNORE = 0x4000, CODE_OUTMOVE = 0x6000,
                    CODE_OUTPOS = 0x8000, CODE_OUTRHOP = 0xA000, CODE_MASKTYPE = 0x1800,
                    CODE_TYPE_MOVING = 0x800, CODE_TYPE_FLOATING = 0x1000, CODE_TYPE_FLUID = 0x1800,
                    CODE_MASKVALUE = 0x7ff;
@@ -143,6 +143,17 @@ __device__ __forceinline__ float visco_at(const KConst& K, float t, int& pos) {
 // and the EOS of each phase for the divide's press: {rho0, 1/rho0, cteb, gamma}.
 constexpr int NN_MAXPH = 8;
 
+// Periodic boundaries (JSph.cpp:718-730, 2067-2076): passed to the periodic kernels only
+// (sph_periodic.hip, the PERI instantiation of the update), so KConst and every kernel of a
+// case without them stay as they are.
+struct PeriConst {
+  int active;               // PeriActive: bit 1 X, 2 Y, 4 Z
+  unsigned cellmax[3];      // DomCells - 1
+  double inc[3][3];         // PeriXinc, PeriYinc, PeriZinc (own-axis component = -MapRealSize)
+  double domposmin[3];      // DomPosMin = Map_PosMin
+  double mapposmin[3], mapposmax[3];  // Map_PosMin / Map_PosMax (widened by KernelSize)
+};
+
 // Cell grid of the (fixed) divide domain — StDivDataGpu (JCellDivDataGpu.h:26-79).
 // Slab decomposition (sph_slab.hip) along the SLAB AXIS (axis 0: x, axis 1: y): a rank's grid
 // covers the global cells [soff, soff + extent) of that axis (the full extent of the other
@@ -205,6 +216,8 @@ struct DevScalars {
   // Max-reductions (float bits of values >= 0) spread over RED_SLOTS slots so that
   // thousands of waves do not serialise on one address; k_dt folds and clears them.
   unsigned red[4][64];
+  // periodic boundaries (sph_periodic.hip): duplicates after the last RunPeriodic, by type
+  unsigned npbper, npfper;
 };
 // RED_VISCETA: NN max effective viscosity (ViscEtaDtMax, JSphCpuSingle.cpp:633 in the v5.0 solver)
 constexpr int RED_VELMAX2 = 0, RED_ACEMAX2 = 1, RED_VISCDT = 2, RED_VISCETA = 3, RED_SLOTS = 64;
@@ -223,7 +236,10 @@ constexpr unsigned ERR_HALO = ERR_HALO_NODE | ERR_HALO_FACE | ERR_HALO_MISS | ER
 // ghost copy to land in, an mDBC ghost node reaching past the ghost columns) halts too: it
 // is folded into the dt all-reduce (folded[4]), so every slab stops at the same step rather
 // than stepping on with incomplete face data.
-constexpr unsigned ERR_FATAL = ERR_DT_NAN | ERR_BOUNDOUT | ERR_HALO;
+// the periodic duplicates of a divide did not fit the particle capacity (sph_periodic.hip):
+// nothing is written past it, the run stops at this step (SPH_FLAG_PERIODIC_FULL)
+constexpr unsigned ERR_PERI_FULL = 128u;
+constexpr unsigned ERR_FATAL = ERR_DT_NAN | ERR_BOUNDOUT | ERR_HALO | ERR_PERI_FULL;
 __device__ __forceinline__ bool halted(const DevScalars* sc) { return (sc->error_flags & ERR_FATAL) != 0u; }
 
 // Wave-level max of a non-negative float, then one atomicMax per wave into a slot

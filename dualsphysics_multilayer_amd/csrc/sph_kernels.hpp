@@ -33,21 +33,51 @@ __device__ __forceinline__ double nc(double x) {
   return x;
 }
 
-// JSphCpu::UpdatePos (JSphCpu.cpp:1240-1293), single domain, no periodic.
+// JSphCpu::UpdatePos (JSphCpu.cpp:1240-1293), single domain.  PERI (a case with periodic
+// boundaries, P set): a particle that left the real map is wrapped on each periodic axis by the
+// whole Peri?inc vector, only the other axes can mark it OUTPOS, and the cell is taken from
+// DomPosMin (JSphCpu.cpp:1254-1291); without PERI the code is what it was before it existed.
 // Returns the new dcell; rcode (optional): the particle's code held in registers, updated in
 // place (else read from a.code when the particle leaves).
+template <bool PERI = false>
 __device__ __forceinline__ unsigned update_pos(const KConst& K, double rx, double ry, double rz, double movx,
                                                double movy, double movz, bool outrhop, unsigned p, const PartArrays& a,
-                                               typecode* rcode_in = nullptr) {
+                                               typecode* rcode_in = nullptr, const PeriConst* P = nullptr) {
   const bool outmove = (fabsf(float(movx)) > K.movlimit || fabsf(float(movy)) > K.movlimit ||
                         fabsf(float(movz)) > K.movlimit);
   rx += movx;
   ry += movy;
   rz += movz;
   if (K.symmetry && ry < 0) ry = -ry;  // Symmetry: reflected across y = 0 (JSphCpu.cpp:1247)
-  const double dx = rx - K.map_realposmin_x, dy = ry - K.map_realposmin_y, dz = rz - K.map_realposmin_z;
-  const bool out = (dx != dx || dy != dy || dz != dz || dx < 0 || dy < 0 || dz < 0 || dx >= K.map_realsize_x ||
-                    dy >= K.map_realsize_y || dz >= K.map_realsize_z);
+  double dx = rx - K.map_realposmin_x, dy = ry - K.map_realposmin_y, dz = rz - K.map_realposmin_z;
+  bool out = (dx != dx || dy != dy || dz != dz || dx < 0 || dy < 0 || dz < 0 || dx >= K.map_realsize_x ||
+              dy >= K.map_realsize_y || dz >= K.map_realsize_z);
+  if constexpr (PERI) {
+    if (out) {
+      const bool px = (P->active & 1) != 0, py = (P->active & 2) != 0, pz = (P->active & 4) != 0;
+      if (px) {
+        if (dx < 0) { dx -= P->inc[0][0]; dy -= P->inc[0][1]; dz -= P->inc[0][2]; }
+        if (dx >= K.map_realsize_x) { dx += P->inc[0][0]; dy += P->inc[0][1]; dz += P->inc[0][2]; }
+      }
+      if (py) {
+        if (dy < 0) { dx -= P->inc[1][0]; dy -= P->inc[1][1]; dz -= P->inc[1][2]; }
+        if (dy >= K.map_realsize_y) { dx += P->inc[1][0]; dy += P->inc[1][1]; dz += P->inc[1][2]; }
+      }
+      if (pz) {
+        if (dz < 0) { dx -= P->inc[2][0]; dy -= P->inc[2][1]; dz -= P->inc[2][2]; }
+        if (dz >= K.map_realsize_z) { dx += P->inc[2][0]; dy += P->inc[2][1]; dz += P->inc[2][2]; }
+      }
+      // (a NaN coordinate fails every comparison: it leaves on its axis only when that axis is
+      // not periodic, as in the reference)
+      const bool outx = !px && (dx < 0 || dx >= K.map_realsize_x);
+      const bool outy = !py && (dy < 0 || dy >= K.map_realsize_y);
+      const bool outz = !pz && (dz < 0 || dz >= K.map_realsize_z);
+      out = outx || outy || outz;
+      rx = dx + K.map_realposmin_x;
+      ry = dy + K.map_realposmin_y;
+      rz = dz + K.map_realposmin_z;
+    }
+  }
   a.posxy[p] = make_double2(rx, ry);
   a.posz[p] = rz;
   if (outrhop || outmove || out) {
@@ -60,7 +90,19 @@ __device__ __forceinline__ unsigned update_pos(const KConst& K, double rx, doubl
     a.dcell[p] = DCELL_OUT;
     return DCELL_OUT;
   }
-  const unsigned cx = unsigned(dx / K.scelld), cy = unsigned(dy / K.scelld), cz = unsigned(dz / K.scelld);
+  if constexpr (PERI) {
+    dx = rx - P->domposmin[0];
+    dy = ry - P->domposmin[1];
+    dz = rz - P->domposmin[2];
+  }
+  unsigned cx = unsigned(dx / K.scelld), cy = unsigned(dy / K.scelld), cz = unsigned(dz / K.scelld);
+  if constexpr (PERI) {
+    // a wrapped particle that is still outside the real map on a periodic axis (a NaN, an
+    // offset beyond one period) stays inside the cell grid
+    cx = min(cx, P->cellmax[0]);
+    cy = min(cy, P->cellmax[1]);
+    cz = min(cz, P->cellmax[2]);
+  }
   const unsigned dc = DcelCell(K.domcellcode, cx, cy, cz);
   a.dcell[p] = dc;
   return dc;
@@ -410,14 +452,32 @@ void launch_fold_maxima(hipStream_t stm, DevScalars* sc, unsigned* folded, bool 
 // cls (not null): the incremental divide's classification rides on the update (sph_incdiv.hpp);
 // pk (not null, with cls): the slab exchange's count pass too (sph_slabpack.hpp)
 struct PackArgs;
+// peri (not null: a case with periodic boundaries; never with cls): the PERI instantiation of
+// the per-particle kernel.
 void launch_verlet(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, bool euler, const float4* arace,
                    PartArrays a, DivGrid g, const float4* shiftpos = nullptr, const IncDivScratch* cls = nullptr,
-                   const PackArgs* pk = nullptr);
+                   const PackArgs* pk = nullptr, const PeriConst* peri = nullptr);
 void launch_sym_pre(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, const float4* arace, PartArrays a,
-                    DivGrid g, const IncDivScratch* cls = nullptr, const PackArgs* pk = nullptr);
+                    DivGrid g, const IncDivScratch* cls = nullptr, const PackArgs* pk = nullptr,
+                    const PeriConst* peri = nullptr);
 void launch_sym_cor(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, const float4* arace, PartArrays a,
                     DivGrid g, const float4* shiftpos = nullptr, const IncDivScratch* cls = nullptr,
-                    const PackArgs* pk = nullptr);
+                    const PackArgs* pk = nullptr, const PeriConst* peri = nullptr);
+
+// ---- periodic boundaries (sph_periodic.hip) ----
+// JSphCpuSingle::RunPeriodic (JSphCpuSingle.cpp:361-431) at the top of a divide: the duplicates
+// of the last divide become CODE_OUTIGNORE (the sort drops them), then per type (bound, fluid),
+// periodic axis (X, Y, Z) and block (the type's new duplicates, then its originals) the listed
+// particles are copied, displaced, after sc->np in the reference's list order (ascending index,
+// +inc before -inc).  Counts stay on the device: sc->np grows, sc->npbper / npfper are set.  A
+// pass that would pass `cap` writes nothing and raises ERR_PERI_FULL.  scan: [peri_scan_words(cap)]
+// u32 scratch.
+size_t peri_scan_words(unsigned cap);
+void launch_run_periodic(hipStream_t stm, unsigned cap, DevScalars* sc, const PeriConst& P, const KConst& K,
+                         const PartArrays& a, bool withm1, bool withpre, unsigned* scan);
+// AceMax over the normal fluid particles only (ComputeAceMax, JSphCpuSingle.cpp:584-605): the
+// reset RED_ACEMAX2 slots from arace of [npb, np).
+void launch_peri_acemax(hipStream_t stm, unsigned cap, DevScalars* sc, const typecode* code, const float4* arace);
 
 // ---- moving boundaries and floating bodies (sph_bodies.hip) ----
 constexpr int MOT_MAXOBJ = 32, MOT_MAXACT = 4, MOT_MAXAXIS = 64;

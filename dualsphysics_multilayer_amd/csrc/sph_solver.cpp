@@ -125,12 +125,41 @@ void derive_constants(const SphCaseDef& c, SphConstants& k) {
   k.scelldiv = (c.cellmode == SPH_CELLMODE_HALF ? 2 : 1);  // cells of 2h (full) or h (half)
   k.scell = k.kernelsize / k.scelldiv;
   k.movlimit = k.scell * 0.9f;
+  // Periodic boundaries (JSph.cpp:718-730, 2067-2076): the own-axis component of each Peri?inc
+  // is -MapRealSize, the cell map is the real map widened by KernelSize on each periodic axis
+  if (c.peri_active < 0 || c.peri_active > 7) throw SphError(SPH_ERR_ARG, "invalid peri_active");
+  k.peri_active = c.peri_active;
+  if (k.peri_active) {
+    if (k.data2d && (k.peri_active & 2)) throw SphError(SPH_ERR_ARG, "Cannot use periodic conditions in Y with 2D simulations");
+    if (c.symmetry && (k.peri_active & 2))
+      throw SphError(SPH_ERR_ARG, "Symmetry is not allowed with periodic conditions in axis Y.");
+  }
   for (int i = 0; i < 3; i++) {
     k.map_realposmin[i] = c.map_realposmin[i];
     k.map_realsize[i] = c.map_realposmax[i] - c.map_realposmin[i];
-    k.dom_posmin[i] = c.map_realposmin[i];
     if (!(k.map_realsize[i] > 0)) throw SphError(SPH_ERR_ARG, "invalid map limits");
-    k.dom_cells[i] = unsigned(std::ceil(k.map_realsize[i] / k.scell));
+    const bool peri = (k.peri_active >> i) & 1;
+    const double pmin = peri ? c.map_realposmin[i] - double(k.kernelsize) : c.map_realposmin[i];
+    const double pmax = peri ? c.map_realposmax[i] + double(k.kernelsize) : c.map_realposmax[i];
+    k.dom_posmin[i] = pmin;
+    // (without periodic axes Map_Size is MapRealSize, the value used before they existed, and
+    // map_posmin / map_posmax stay zero: the map is the real map)
+    const double mapsize = peri ? pmax - pmin : k.map_realsize[i];
+    if (k.peri_active) {
+      k.map_posmin[i] = pmin;
+      k.map_posmax[i] = pmax;
+    }
+    k.dom_cells[i] = unsigned(std::ceil(mapsize / k.scell));
+    // a period of at most 2 KernelSize would make a particle a neighbour of its own image, and
+    // the duplicates of one pass would not be the whole rim (not a case the reference foresees)
+    if (peri && !(k.map_realsize[i] > 2.0 * double(k.kernelsize)))
+      throw SphError(SPH_ERR_ARG, "periodic boundaries: a periodic axis must be longer than twice the interaction distance");
+    if (peri) {
+      const double* in = (i == 0 ? c.peri_xinc : i == 1 ? c.peri_yinc : c.peri_zinc);
+      double* out = (i == 0 ? k.peri_xinc : i == 1 ? k.peri_yinc : k.peri_zinc);
+      for (int j = 0; j < 3; j++) out[j] = in[j];
+      out[i] = -k.map_realsize[i];
+    }
   }
   k.dom_cellcode = cell_code(k.dom_cells[0] + 1, k.dom_cells[1] + 1, k.dom_cells[2] + 1);
   if (!k.dom_cellcode) throw SphError(SPH_ERR_ARG, "failed to select a valid CellCode");
@@ -296,6 +325,54 @@ static KConst make_kconst(const SphConstants& c) {
     K.ddte4 = float(r0 * a * (a - 1) * (a - 2) * (a - 3) / 24 * gz * gz * gz * gz);
   }
   return K;
+}
+
+static PeriConst make_periconst(const SphConstants& c) {
+  PeriConst P;
+  std::memset(&P, 0, sizeof(P));
+  P.active = c.peri_active;
+  for (int i = 0; i < 3; i++) {
+    P.cellmax[i] = c.dom_cells[i] ? c.dom_cells[i] - 1u : 0u;
+    P.inc[0][i] = c.peri_xinc[i];
+    P.inc[1][i] = c.peri_yinc[i];
+    P.inc[2][i] = c.peri_zinc[i];
+    P.domposmin[i] = c.dom_posmin[i];
+    P.mapposmin[i] = c.map_posmin[i];
+    P.mapposmax[i] = c.map_posmax[i];
+  }
+  return P;
+}
+
+// RunPeriodic on the host for the initial particles (JSphCpuSingle.cpp:361-431, counts only):
+// the duplicates of the first divide, which size the particle capacity.
+static unsigned initial_periodic_count(const SphConstants& C, const SphParticlesHost& h, unsigned npb) {
+  const PeriConst P = make_periconst(C);
+  struct V3 { double x, y, z; };
+  auto inside = [&](const V3& q) {
+    return P.mapposmin[0] <= q.x && P.mapposmin[1] <= q.y && P.mapposmin[2] <= q.z && q.x < P.mapposmax[0] &&
+           q.y < P.mapposmax[1] && q.z < P.mapposmax[2];
+  };
+  unsigned long long total = 0;
+  for (int type = 0; type < 2; type++) {
+    std::vector<V3> made;  // the type's new duplicates, in list order
+    const unsigned p0 = type ? npb : 0u, p1 = type ? h.n : npb;
+    for (int ax = 0; ax < 3; ax++) {
+      if (!(P.active & (1 << ax))) continue;
+      const V3 inc{P.inc[ax][0], P.inc[ax][1], P.inc[ax][2]};
+      std::vector<V3> add;
+      auto list = [&](const V3& q) {
+        const V3 a{q.x + inc.x, q.y + inc.y, q.z + inc.z}, b{q.x - inc.x, q.y - inc.y, q.z - inc.z};
+        if (inside(a)) add.push_back(a);
+        if (inside(b)) add.push_back(b);
+      };
+      for (const V3& q : made) list(q);
+      for (unsigned p = p0; p < p1; p++) list(V3{h.pos[3 * p], h.pos[3 * p + 1], h.pos[3 * p + 2]});
+      made.insert(made.end(), add.begin(), add.end());
+    }
+    total += made.size();
+  }
+  if (total > 0x7fffffffull) throw SphError(SPH_ERR_ARG, "The number of particles is too big.");
+  return unsigned(total);
 }
 
 // Ghost columns per slab face: the support radius 2h is one full cell or two half cells
@@ -484,6 +561,36 @@ void SphGpuSingle::Init(const SphCaseDef& cdef, const SphParticlesHost& init) {
   if (const char* e = std::getenv("SPH_SLAB_CUT")) cut_items_ = slab() && std::atoi(e) != 0;
   if (slab_mincap_ || cut_items_) test_hook_notice(slab_mincap_ ? "SPH_SLAB_MINCAP" : "SPH_SLAB_CUT");
   cap_ = slab() ? n + (slab_mincap_ ? 16u : std::max(n / 2, 65536u)) : n;
+  // Periodic boundaries: single domain, DBC, one phase, artificial viscosity, no bodies (the
+  // set_* calls refuse those).  The duplicates live behind the normal particles, and at a
+  // divide the new ones are appended while the previous divide's still hold their slots (the
+  // sort drops those): the capacity is the normal particles + twice the first divide's
+  // duplicates + head-room (half as many again, at least 4096), sized once; a divide that
+  // needs more stops the run (ERR_PERI_FULL).
+  peri_ = C.peri_active != 0;
+  if (peri_) {
+    if (slab()) throw SphError(SPH_ERR_UNSUPPORTED, "periodic boundaries are not implemented for slab solvers");
+    if (C.tboundary == SPH_BOUND_MDBC) throw SphError(SPH_ERR_UNSUPPORTED, "periodic boundaries with mDBC are not implemented");
+    if (C.rheology == SPH_RHEOLOGY_NN)
+      throw SphError(SPH_ERR_UNSUPPORTED, "periodic boundaries with NN multiphase are not implemented");
+    if (C.tvisco != SPH_VISCO_ARTIFICIAL || C.shift_mode != SPH_SHIFT_NONE)
+      throw SphError(SPH_ERR_UNSUPPORTED, "periodic boundaries with Laminar+SPS or shifting are not implemented");
+    if (C.symmetry) throw SphError(SPH_ERR_UNSUPPORTED, "periodic boundaries with Symmetry are not implemented");
+    if (init.code)
+      for (unsigned p = 0; p < init.n; p++) {
+        const typecode t = CodeType(init.code[p]);
+        if (t == CODE_TYPE_MOVING || t == CODE_TYPE_FLOATING)
+          throw SphError(SPH_ERR_UNSUPPORTED,
+                         "periodic boundaries with moving boundaries or floating bodies are not implemented");
+      }
+    P_ = make_periconst(C);
+    const unsigned ndup = initial_periodic_count(C, init, cdef.npb);
+    if (const char* e = std::getenv("SPH_PERI_MINCAP")) peri_mincap_ = std::atoi(e) != 0;
+    if (peri_mincap_) test_hook_notice("SPH_PERI_MINCAP");
+    const unsigned long long want = 0ull + n + 2ull * ndup + (peri_mincap_ ? 0u : std::max(ndup / 2, 4096u));
+    if (want >= (1ull << 31)) throw SphError(SPH_ERR_ARG, "The number of particles is too big.");
+    cap_ = unsigned(want);
+  }
   keybits_ = bits_for(G.boxdiscard, 1);
   // grid-sized buffers hold the widest grid a slab can get from a re-partition (all cells
   // of the slab axis + W = ghost_width ghost cells per face), so they never move
@@ -500,6 +607,9 @@ void SphGpuSingle::Init(const SphCaseDef& cdef, const SphParticlesHost& init) {
   // again per divide for a re-partitioned slab; ncy >= 3 or a single y row), 30-bit counts
   inc_ok_ = G.ncx >= 3 && (G.ncy >= 3 || G.ncy == 1) && n < (1u << 29);
   if (const char* e = std::getenv("SPH_DIVIDE")) inc_ok_ = inc_ok_ && std::string(e) != "full";
+  // periodic cases take the full sort every divide, as the reference does with PeriActive
+  // (JCellDivCpuSingle.cpp:298): the duplicates are appended behind np and re-sorted
+  if (peri_) inc_ok_ = false;
   if (const char* e = std::getenv("SPH_CLS_SPLIT")) cls_split_ = std::atoi(e) != 0;
   if (cls_split_) test_hook_notice("SPH_CLS_SPLIT");
   // The tiled kernel stages the 3x3 rows of 3 cells of CellMode=full, or the 5x5 rows of
@@ -733,6 +843,7 @@ void SphGpuSingle::AllocParticles(unsigned cap) {
   sort_.hist = (unsigned*)dmalloc(4 * size_t(sort_.ntiles) * (1u << RS_MAXBITS));
   // slab pack tile counts: tilecnt[7][ntiles] (ghost L/R, migrant L/R, staying, face ghosts L/R; sph_slab.hip)
   packtiles_ = (unsigned*)dmalloc(PK_TILECNT_BYTES(n));
+  if (peri_) periscan_ = (unsigned*)dmalloc(4 * peri_scan_words(cap));
   cap_ = cap;
 }
 
@@ -851,8 +962,12 @@ void SphGpuSingle::Upload(const SphParticlesHost& h, const std::vector<unsigned>
       throw SphError(SPH_ERR_ARG, "Initial fluid density is out of limits.");
     // JSph::LoadDcellParticles (JSph.cpp:1690-1711).
     const double dx = x - C.dom_posmin[0], dy = y - C.dom_posmin[1], dz = z - C.dom_posmin[2];
-    if (!(dx >= 0 && dy >= 0 && dz >= 0 && dx < C.map_realsize[0] && dy < C.map_realsize[1] && dz < C.map_realsize[2]))
-      throw SphError(SPH_ERR_ARG, "Found new particles out.");
+    {  // inside the real map (without periodic axes DomPosMin is MapRealPosMin: the same values)
+      const double rx = peri_ ? x - C.map_realposmin[0] : dx, ry = peri_ ? y - C.map_realposmin[1] : dy,
+                   rz = peri_ ? z - C.map_realposmin[2] : dz;
+      if (!(rx >= 0 && ry >= 0 && rz >= 0 && rx < C.map_realsize[0] && ry < C.map_realsize[1] && rz < C.map_realsize[2]))
+        throw SphError(SPH_ERR_ARG, "Found new particles out.");
+    }
     dcell[i] = DcelCell(C.dom_cellcode, unsigned(dx / double(C.scell)), unsigned(dy / double(C.scell)),
                         unsigned(dz / double(C.scell)));
   }
@@ -1266,6 +1381,8 @@ void SphGpuSingle::RunCellDivide() {
   }
   const unsigned ngl = ghosts ? unsigned(xg_rl_) : 0u, ngr = ghosts ? unsigned(xg_rr_) : 0u;
   const bool withm1 = (step_algorithm_ == SPH_STEP_VERLET);
+  // RunPeriodic before every divide, the in-step one of Symplectic included (JSphCpuSingle.cpp:444)
+  if (peri_) launch_run_periodic(stream, cap_, sc_, P_, K, cur_, withm1, havepre_, periscan_);
   // Items (each build also zeroes its queues).  With the overlap a slab cuts its rows where
   // the stencil (scelldiv columns) stops reaching a ghost column: the interior list runs
   // while the ghost records are in flight, the face list (items of <= scelldiv columns) after
@@ -1474,6 +1591,12 @@ void SphGpuSingle::Interaction_Forces(int interstep) {
     check_hip(hipMemsetAsync(&sc_->red[RED_ACEMAX2][0], 0, 4 * RED_SLOTS, stream), "reset acemax");
     launch_accinput(stream, cap_, sc_, K, G, acc_, accrows_, accstate_, accvals_, interstep, cur_, arace_);
   }
+  if (peri_) {
+    // AceMax over the normal particles only (ComputeAceMax, JSphCpuSingle.cpp:584-605): a
+    // duplicate in the rim beyond the real map lacks the neighbours further out
+    check_hip(hipMemsetAsync(&sc_->red[RED_ACEMAX2][0], 0, 4 * RED_SLOTS, stream), "reset acemax");
+    launch_peri_acemax(stream, cap_, sc_, cur_.code, arace_);
+  }
   TimedEnd(0);
   if (turn && fold_turn_ >= 0) {  // the next DtVariable's fold, inside this slab's turn
     launch_fold_maxima(stream, sc_, folded_, fold_turn_ != 0);
@@ -1575,7 +1698,8 @@ void SphGpuSingle::ComputeVerlet() {
   verletstep_++;
   const bool euler = !(verletstep_ < C.verlet_steps);
   const UpdateFuse fu = FuseUpdate(false);
-  launch_verlet(stream, cap_, sc_, K, euler, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk);
+  launch_verlet(stream, cap_, sc_, K, euler, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk,
+                peri_ ? &P_ : nullptr);
   if (euler) verletstep_ = 0;
   std::swap(cur_.velrhop, cur_.velrhopm1);
   TimedEnd(1);
@@ -1590,7 +1714,7 @@ void SphGpuSingle::ComputeSymplecticPre() {
   std::swap(cur_.velrhop, cur_.velrhoppre);
   havepre_ = true;
   const UpdateFuse fu = FuseUpdate(true);
-  launch_sym_pre(stream, cap_, sc_, K, arace_, cur_, G, fu.cls, fu.pk);
+  launch_sym_pre(stream, cap_, sc_, K, arace_, cur_, G, fu.cls, fu.pk, peri_ ? &P_ : nullptr);
   TimedEnd(1);
   UpdateTurn(false);
 }
@@ -1599,7 +1723,8 @@ void SphGpuSingle::ComputeSymplecticCorr() {
   UpdateTurn(true);
   TimedBegin(1);
   const UpdateFuse fu = FuseUpdate(false);
-  launch_sym_cor(stream, cap_, sc_, K, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk);
+  launch_sym_cor(stream, cap_, sc_, K, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk,
+                 peri_ ? &P_ : nullptr);
   havepre_ = false;
   TimedEnd(1);
   UpdateTurn(false);
@@ -1893,6 +2018,7 @@ void SphGpuSingle::RunGauges() {
 
 void SphGpuSingle::SetGauges(unsigned n, const SphGaugeDef* defs, unsigned record_capacity) {
   if (slab()) throw SphError(SPH_ERR_UNSUPPORTED, "gauges run on a single domain only (not on slabs)");
+  if (peri_) throw SphError(SPH_ERR_UNSUPPORTED, "gauges with periodic boundaries are not implemented");
   if (nn_) throw SphError(SPH_ERR_UNSUPPORTED, "gauges with NN multiphase are not implemented");
   if (stepped_ || gauges_.ng) throw SphError(SPH_ERR_STATE, "the gauges are configured once, before the first step");
   if (!n || !defs) throw SphError(SPH_ERR_ARG, "no gauges");
@@ -2059,6 +2185,7 @@ void SphGpuSingle::SetMotion(unsigned nobj, unsigned nmov, const SphMotionMov* m
 // it every step.
 void SphGpuSingle::SetMotionTree(unsigned nnode, const SphMotionObj* nodes, unsigned nmov, const SphMotionMov* movs,
                                  unsigned nevt, const SphMotionEvent* evts, unsigned nrows, const double* rows) {
+  if (peri_) throw SphError(SPH_ERR_UNSUPPORTED, "moving boundaries with periodic boundaries are not implemented");
   if (stepped_ || motion_) throw SphError(SPH_ERR_STATE, "the motion is configured once, before the first step");
   if (!nnode || nnode > unsigned(MOT_MAXOBJ)) throw SphError(SPH_ERR_UNSUPPORTED, "number of motion objects out of range");
   if ((nmov && !movs) || (nevt && !evts) || (nrows && !rows)) throw SphError(SPH_ERR_ARG, "motion arrays missing");
@@ -2192,6 +2319,7 @@ void SphGpuSingle::SetMotionTree(unsigned nnode, const SphMotionObj* nodes, unsi
 
 // JSph::LoadCaseConfig floating objects (JSph.cpp:1046-1100).
 void SphGpuSingle::SetFloatings(unsigned nft, const SphFloatingDef* defs, double ftpause) {
+  if (peri_) throw SphError(SPH_ERR_UNSUPPORTED, "floating bodies with periodic boundaries are not implemented");
   if (stepped_ || ftbodies_) throw SphError(SPH_ERR_STATE, "the floating bodies are configured once, before the first step");
   if (!nft || !defs) throw SphError(SPH_ERR_ARG, "no floating bodies");
   if (nn_) {
@@ -2394,6 +2522,13 @@ SphRunStats SphGpuSingle::Stats() {
   r.np = (slab() && (transport_->has_left() || transport_->has_right())) ? s.nown : s.np;
   r.npb = s.npb;
   r.npbok = s.npbok;
+  if (peri_) {  // normal particles only: the duplicates sit among them in the cells
+    r.npbper = s.npbper;
+    r.npfper = s.npfper;
+    r.np = s.np - s.npbper - s.npfper;
+    r.npb = s.npb - s.npbper;
+    r.npbok = s.npbok - std::min(s.npbok, s.npbper);
+  }
   r.nout = s.nout;
   r.dtmodif = s.dtmodif;
   r.error_flags = s.error_flags;
@@ -2424,6 +2559,9 @@ void SphGpuSingle::CheckErrors() {
   const SphRunStats s = Stats();
   if (s.error_flags & ERR_BOUNDOUT) throw SphError(SPH_ERR_BOUNDOUT, "boundary particles were excluded (AbortBoundOut)");
   if (s.error_flags & ERR_DT_NAN) throw SphError(SPH_ERR_DT, "The computed Dt is NaN or infinity");
+  if (s.error_flags & ERR_PERI_FULL)
+    throw SphError(SPH_ERR_NOMEM, "the periodic duplicates of a divide exceed the particle capacity (step " +
+                                      std::to_string(s.nstep) + ")");
   if (s.error_flags & ERR_HALO_NODE)
     throw SphError(SPH_ERR_UNSUPPORTED, "slab halo: an mDBC ghost node needs particles beyond the slab's ghost columns");
   if (s.error_flags & ERR_HALO_FACE)
@@ -2467,6 +2605,8 @@ void SphGpuSingle::Download(SphParticlesHost& out) {
     if (slab()) {  // owned particles only
       if (!slab_owned(G, slab_local(G, C.dom_cellcode, dcell[p]))) continue;
     }
+    if (peri_ && !CodeIsNormal(code[p])) continue;  // normal particles only (GetParticlesData onlynormal)
+    if (k >= out.n) throw SphError(SPH_ERR_STATE, "owned particle count mismatch");
     if (out.idp) out.idp[k] = idp[p];
     if (out.code) out.code[k] = code[p];
     if (out.pos) { out.pos[3 * k] = pxy[p].x; out.pos[3 * k + 1] = pxy[p].y; out.pos[3 * k + 2] = pz[p]; }
@@ -2487,12 +2627,23 @@ void SphGpuSingle::DownloadInteraction(SphInterOut& out) {
   if (sps_) std::swap(cur_.tau, taunew_);
   DtVariable(DT_PEEK);
   const SphRunStats s = Stats();
-  std::vector<float4> a(s.np);
-  check_hip(hipMemcpy(a.data(), arace_, 16 * size_t(s.np), hipMemcpyDeviceToHost), "download arace");
-  for (unsigned p = 0; p < s.np; p++) {
-    if (out.ar) out.ar[p] = a[p].w;
-    if (out.ace) { out.ace[3 * p] = a[p].x; out.ace[3 * p + 1] = a[p].y; out.ace[3 * p + 2] = a[p].z; }
+  const unsigned nheld = sc_host_->np;  // with periodic boundaries: the duplicates too
+  std::vector<float4> a(nheld);
+  check_hip(hipMemcpy(a.data(), arace_, 16 * size_t(nheld), hipMemcpyDeviceToHost), "download arace");
+  std::vector<typecode> code;
+  if (peri_) {
+    code.resize(nheld);
+    check_hip(hipMemcpy(code.data(), cur_.code, 2 * size_t(nheld), hipMemcpyDeviceToHost), "download code");
   }
+  unsigned k = 0;
+  for (unsigned p = 0; p < nheld; p++) {
+    if (peri_ && !CodeIsNormal(code[p])) continue;  // normal particles, in device order
+    if (k >= s.np) throw SphError(SPH_ERR_STATE, "normal particle count mismatch");
+    if (out.ar) out.ar[k] = a[p].w;
+    if (out.ace) { out.ace[3 * k] = a[p].x; out.ace[3 * k + 1] = a[p].y; out.ace[3 * k + 2] = a[p].z; }
+    k++;
+  }
+  if (k != s.np) throw SphError(SPH_ERR_STATE, "normal particle count mismatch");
   out.velmax = s.velmax;
   out.acemax = s.acemax;
   out.viscdtmax = s.viscdtmax;

@@ -295,6 +295,12 @@ class SphGpuSingle {
   double* accrows_ = nullptr;
   AccState* accstate_ = nullptr;
   AccVals* accvals_ = nullptr;
+  // periodic boundaries (sph_periodic.hip): the constants of the periodic kernels, the scratch
+  // of RunPeriodic's passes; SPH_PERI_MINCAP (test hook): no head-room over the first divide's
+  // duplicates
+  bool peri_ = false, peri_mincap_ = false;
+  PeriConst P_{};
+  unsigned* periscan_ = nullptr;
   DampZoneDev* dampzones_ = nullptr;  // damping zones in list order (ndamp_ = 0: none, nothing launched)
   int ndamp_ = 0;
   // turns measurement mode: the dt maxima of the next DtVariable are folded at the end of the

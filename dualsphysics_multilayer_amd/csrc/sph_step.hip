@@ -197,9 +197,12 @@ __device__ __forceinline__ void upd_keep(const UpdIn& in) {
 
 // ComputeVerlet (JSphCpu.cpp:1381-1399): bound -> ComputeVelrhopBound, fluid -> ComputeVerletVarsFluid.
 // New values are written in velrhopm1 (the caller swaps velrhop/velrhopm1 afterwards).
+// PERI (periodic boundaries): the duplicates are updated like any particle, as the reference's
+// ComputeVerletVarsFluid does (JSphCpu.cpp:1310-1356); the next RunPeriodic drops them.
+template <bool PERI = false>
 __device__ __forceinline__ UpdOut verlet_part(const DevScalars* __restrict__ sc, const KConst& K, int euler,
                                               const PartArrays& a, const DivGrid& g, bool shift, unsigned p,
-                                              unsigned npb, const UpdIn& in) {
+                                              unsigned npb, const UpdIn& in, const PeriConst* P = nullptr) {
   UpdOut o{in.dcell, in.code};
   const bool ghost = slab_ghost(K, g, in.dcell);
   if (ghost) {
@@ -237,7 +240,7 @@ __device__ __forceinline__ UpdOut verlet_part(const DevScalars* __restrict__ sc,
   const float4 nv = make_float4(float(double(vr2.x) + nc(agx * dt2)), float(double(vr2.y) + nc(agy * dt2)),
                                 float(double(vr2.z) + nc(agz * dt2)), rhopnew);
   typecode rcode = in.code;
-  o.dcell = update_pos(K, in.pxy.x, in.pxy.y, in.pz, dx, dy, dz, outrhop, p, a, &rcode);
+  o.dcell = update_pos<PERI>(K, in.pxy.x, in.pxy.y, in.pz, dx, dy, dz, outrhop, p, a, &rcode, P);
   o.code = rcode;
   a.velrhopm1[p] = nv;
   return o;
@@ -245,9 +248,12 @@ __device__ __forceinline__ UpdOut verlet_part(const DevScalars* __restrict__ sc,
 
 // ComputeSymplecticPre (JSphCpu.cpp:1406-1504).  The caller has already moved the
 // current pos/velrhop into the *pre arrays (pointer swap); new values go to pos/velrhop.
+// PERI: a periodic duplicate gets its new velocity and density but is not displaced, and only
+// normal particles are marked OUTRHOP (JSphCpu.cpp:1473,1488).
+template <bool PERI = false>
 __device__ __forceinline__ UpdOut sym_pre_part(const DevScalars* __restrict__ sc, const KConst& K,
                                                const PartArrays& a, const DivGrid& g, unsigned p, unsigned npb,
-                                               const UpdIn& in) {
+                                               const UpdIn& in, const PeriConst* P = nullptr) {
   UpdOut o{in.dcell, in.code};
   const bool ghost = slab_ghost(K, g, in.dcell);
   if (ghost) {  // ghosts are dropped all the same, halted or not (verlet_part)
@@ -289,8 +295,11 @@ __device__ __forceinline__ UpdOut sym_pre_part(const DevScalars* __restrict__ sc
     rcode = CodeSetNormal(rcode) | CODE_OUTRHOP;
     a.code[p] = rcode;
   }
-  if (CodeIsFluid(rcode)) {
-    o.dcell = update_pos(K, pxy.x, pxy.y, pz, dx, dy, dz, CodeIsOutRhop(rcode), p, a, &rcode);
+  if (PERI && CodeSpecial(rcode) == CODE_PERIODIC) {  // not displaced (dropped by the next RunPeriodic)
+    a.posxy[p] = pxy;
+    a.posz[p] = pz;
+  } else if (CodeIsFluid(rcode)) {
+    o.dcell = update_pos<PERI>(K, pxy.x, pxy.y, pz, dx, dy, dz, CodeIsOutRhop(rcode), p, a, &rcode, P);
   } else {
     a.posxy[p] = pxy;
     a.posz[p] = pz;
@@ -300,9 +309,11 @@ __device__ __forceinline__ UpdOut sym_pre_part(const DevScalars* __restrict__ sc
 }
 
 // ComputeSymplecticCorr (JSphCpu.cpp:1510-1606).
+// PERI: as the predictor (JSphCpu.cpp:1574,1590).
+template <bool PERI = false>
 __device__ __forceinline__ UpdOut sym_cor_part(const DevScalars* __restrict__ sc, const KConst& K,
                                                const PartArrays& a, const DivGrid& g, bool shift, unsigned p,
-                                               unsigned npb, const UpdIn& in) {
+                                               unsigned npb, const UpdIn& in, const PeriConst* P = nullptr) {
   UpdOut o{in.dcell, in.code};
   if (slab_ghost(K, g, in.dcell)) {  // ghosts dropped even when halted
     a.dcell[p] = DCELL_DISCARD;
@@ -342,8 +353,11 @@ __device__ __forceinline__ UpdOut sym_cor_part(const DevScalars* __restrict__ sc
     a.code[p] = rcode;
   }
   a.velrhop[p] = nv;
-  if (CodeIsFluid(rcode)) {
-    o.dcell = update_pos(K, in.pxy.x, in.pxy.y, in.pz, dx, dy, dz, CodeIsOutRhop(rcode), p, a, &rcode);
+  if (PERI && CodeSpecial(rcode) == CODE_PERIODIC) {
+    a.posxy[p] = in.pxy;
+    a.posz[p] = in.pz;
+  } else if (CodeIsFluid(rcode)) {
+    o.dcell = update_pos<PERI>(K, in.pxy.x, in.pxy.y, in.pz, dx, dy, dz, CodeIsOutRhop(rcode), p, a, &rcode, P);
   } else {
     a.posxy[p] = in.pxy;
     a.posz[p] = in.pz;
@@ -353,13 +367,13 @@ __device__ __forceinline__ UpdOut sym_cor_part(const DevScalars* __restrict__ sc
 }
 
 // One particle's update of kind KIND from its loaded inputs (the kind's arithmetic and stores).
-template <int KIND>
+template <int KIND, bool PERI = false>
 __device__ __forceinline__ UpdOut upd_compute(const DevScalars* __restrict__ sc, const KConst& K, int euler,
                                               const PartArrays& a, const DivGrid& g, bool shift, unsigned p,
-                                              unsigned npb, const UpdIn& in) {
-  if (KIND == UPD_VERLET) return verlet_part(sc, K, euler, a, g, shift, p, npb, in);
-  if (KIND == UPD_SYM_PRE) return sym_pre_part(sc, K, a, g, p, npb, in);
-  return sym_cor_part(sc, K, a, g, shift, p, npb, in);
+                                              unsigned npb, const UpdIn& in, const PeriConst* P = nullptr) {
+  if (KIND == UPD_VERLET) return verlet_part<PERI>(sc, K, euler, a, g, shift, p, npb, in, P);
+  if (KIND == UPD_SYM_PRE) return sym_pre_part<PERI>(sc, K, a, g, p, npb, in, P);
+  return sym_cor_part<PERI>(sc, K, a, g, shift, p, npb, in, P);
 }
 
 template <int KIND>
@@ -372,6 +386,19 @@ __global__ __launch_bounds__(256) void k_update(const DevScalars* __restrict__ s
   const UpdIn in = upd_load<KIND>(euler, arace, a, shiftpos, p, npb);
   upd_keep(in);
   upd_compute<KIND>(sc, K, euler, a, g, shiftpos != nullptr, p, npb, in);
+}
+
+// A case with periodic boundaries (its divide is the full sort: no classification rides here).
+template <int KIND>
+__global__ __launch_bounds__(256) void k_update_peri(const DevScalars* __restrict__ sc, KConst K, int euler,
+                                                     const float4* __restrict__ arace, PartArrays a, DivGrid g,
+                                                     const float4* __restrict__ shiftpos, PeriConst P) {
+  const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= sc->np) return;
+  const unsigned npb = sc->npb;
+  const UpdIn in = upd_load<KIND>(euler, arace, a, shiftpos, p, npb);
+  upd_keep(in);
+  upd_compute<KIND, true>(sc, K, euler, a, g, shiftpos != nullptr, p, npb, in, &P);
 }
 
 // The update with the incremental divide's classification of the same particles (sph_incdiv.hpp):
@@ -436,30 +463,45 @@ static void launch_update_cls(hipStream_t stm, DevScalars* sc, const KConst& K, 
 // cls: the divide's scratch when the classification rides on the update (nullptr: the
 // per-particle kernel, the divide classifies).
 void launch_verlet(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, bool euler, const float4* arace,
-                   PartArrays a, DivGrid g, const float4* shiftpos, const IncDivScratch* cls, const PackArgs* pk) {
+                   PartArrays a, DivGrid g, const float4* shiftpos, const IncDivScratch* cls, const PackArgs* pk,
+                   const PeriConst* peri) {
   if (cls) {
     launch_update_cls<UPD_VERLET>(stm, sc, K, int(euler), arace, a, g, shiftpos, *cls, pk);
     return;
   }
   const unsigned nb = (cap + 255) / 256;
+  if (peri) {
+    hipLaunchKernelGGL(k_update_peri<UPD_VERLET>, dim3(nb), dim3(256), 0, stm, sc, K, int(euler), arace, a, g,
+                       shiftpos, *peri);
+    return;
+  }
   hipLaunchKernelGGL(k_update<UPD_VERLET>, dim3(nb), dim3(256), 0, stm, sc, K, int(euler), arace, a, g, shiftpos);
 }
 void launch_sym_pre(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, const float4* arace, PartArrays a,
-                    DivGrid g, const IncDivScratch* cls, const PackArgs* pk) {
+                    DivGrid g, const IncDivScratch* cls, const PackArgs* pk, const PeriConst* peri) {
   if (cls) {
     launch_update_cls<UPD_SYM_PRE>(stm, sc, K, 0, arace, a, g, nullptr, *cls, pk);
     return;
   }
   const unsigned nb = (cap + 255) / 256;
+  if (peri) {
+    hipLaunchKernelGGL(k_update_peri<UPD_SYM_PRE>, dim3(nb), dim3(256), 0, stm, sc, K, 0, arace, a, g, nullptr, *peri);
+    return;
+  }
   hipLaunchKernelGGL(k_update<UPD_SYM_PRE>, dim3(nb), dim3(256), 0, stm, sc, K, 0, arace, a, g, nullptr);
 }
 void launch_sym_cor(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, const float4* arace, PartArrays a,
-                    DivGrid g, const float4* shiftpos, const IncDivScratch* cls, const PackArgs* pk) {
+                    DivGrid g, const float4* shiftpos, const IncDivScratch* cls, const PackArgs* pk,
+                    const PeriConst* peri) {
   if (cls) {
     launch_update_cls<UPD_SYM_COR>(stm, sc, K, 0, arace, a, g, shiftpos, *cls, pk);
     return;
   }
   const unsigned nb = (cap + 255) / 256;
+  if (peri) {
+    hipLaunchKernelGGL(k_update_peri<UPD_SYM_COR>, dim3(nb), dim3(256), 0, stm, sc, K, 0, arace, a, g, shiftpos, *peri);
+    return;
+  }
   hipLaunchKernelGGL(k_update<UPD_SYM_COR>, dim3(nb), dim3(256), 0, stm, sc, K, 0, arace, a, g, shiftpos);
 }
 

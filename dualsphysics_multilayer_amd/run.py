@@ -178,7 +178,10 @@ class CaseRun:
                     dp=c.dp, h=c.h, b=c.cteb, rhop0=c.rhop0, gamma=c.gamma, massbound=c.massbound,
                     massfluid=c.massfluid, map_posmin=list(cd["map_realposmin"]),
                     map_posmax=list(cd["map_realposmax"]), case_posmin=list(c.case_posmin),
-                    case_posmax=list(c.case_posmax), pos_double=int(self.sv_pos_double), peri_mode=0,
+                    case_posmax=list(c.case_posmax), pos_double=int(self.sv_pos_double),
+                    # TpPeri = PeriActive and the derived Peri?inc (JSph.cpp:2390 ConfigSimPeri)
+                    peri_mode=int(self.k["peri_active"]), peri_xinc=list(self.k["peri_xinc"]),
+                    peri_yinc=list(self.k["peri_yinc"]), peri_zinc=list(self.k["peri_zinc"]),
                     visco_type=1, visco=float(np.float32(c.visco)),
                     viscoboundfactor=float(np.float32(c.viscoboundfactor)),
                     gravity=[float(np.float32(g)) for g in c.gravity], mkbound=fb[0]["mk"], mkfluid=fl[0]["mk"],

@@ -4,7 +4,7 @@
 Mirrors what ``JSph`` reads before the first step, restricted to what the hot path of
 this core runs (fixed and moving DBC/mDBC boundaries, RigidAlgorithm=1 floating bodies, fluid,
 Wendland, artificial viscosity, DDT 0-3,
-Verlet / Symplectic, no periodicity); anything else raises ``CaseError`` the way the
+Verlet / Symplectic, periodic boundaries); anything else raises ``CaseError`` the way the
 reference refuses an invalid configuration, never silently ignored:
 
 * constants  — ``JCaseCtes::ReadXmlRun`` (JCaseCtes.cpp:201-215) via
@@ -413,6 +413,18 @@ class XmlCase:
                 raise CaseError("Symmetry is not allowed with floating bodies.")
             if self.tvisco != 1:
                 raise CaseError("Symmetry is only allowed with Artificial viscosity.")
+        if self.peri_active:
+            if self.symmetry and self.peri_active & 2:  # JSph.cpp:1176
+                raise CaseError("Symmetry is not allowed with periodic conditions in axis Y.")
+            # what this core runs with periodic boundaries: DBC, artificial viscosity, one phase,
+            # fixed boundaries only, no gauges
+            bad = [what for on, what in (
+                (self.symmetry, "Symmetry"), (self.tboundary == 2, "mDBC"), (self.rheology == 2, "NN multiphase"),
+                (self.tvisco != 1, "Laminar+SPS viscosity"), (self.shift_mode != 0, "Shifting"),
+                (bool(self.case_nmoving), "Moving boundaries"), (bool(self.case_nfloat), "Floating bodies"),
+                (bool(self.gauges), "<special><gauges>")) if on]
+            if bad:
+                raise CaseError(f"{', '.join(bad)} with periodic boundaries: not supported by this core.")
         # -- particles (JPartsLoad4::LoadParticles) ------------------------------------
         self.partbegin = int(partbegin)
         self.partbegin_dir = None
@@ -441,6 +453,8 @@ class XmlCase:
         self.npb = int(isb.sum())
         if self.npb != self.case_npb:
             raise CaseError(f"{fn}: {self.npb} boundary particles loaded, the case has {self.case_npb}.")
+        if self.peri_active and not self.partbegin:
+            self._check_periodic_walls()
         if self.floatings and self.partbegin:
             self._restart_floatings()
         if self.floatings and self.rigidalgorithm != 1:
@@ -454,9 +468,15 @@ class XmlCase:
             self._map = (np.array(h["map_posmin"]), np.array(h["map_posmax"]))
         else:
             border = float(np.float32(self.h)) * BORDER_MAP
-            rmin = [c - border for c in cmin]
-            rmax = [c + border for c in cmax]
+            # a periodic axis: border Dp/2 (JPartsLoad4::CalculeLimits) and no <simulationdomain>
+            # (JSph::ResizeMapLimits, JSph.cpp:1382-1384)
+            bor = [self.dp / 2.0 if self.peri_active >> i & 1 else border for i in range(3)]
+            rmin = [cmin[i] - bor[i] for i in range(3)]
+            rmax = [cmax[i] + bor[i] for i in range(3)]
             dmin, dmax = self._domain.resize(rmin, rmax, self.data2d)
+            for i in range(3):
+                if self.peri_active >> i & 1:
+                    dmin[i], dmax[i] = rmin[i], rmax[i]
             if self.symmetry:
                 dmin[1] = 0.0  # JSph::ResizeMapLimits (JSph.cpp:1386)
             self._map = (np.array(dmin), np.array(dmax))
@@ -619,10 +639,25 @@ class XmlCase:
         self.rhopoutmax = p.num("RhopOutMax") if p.exists("RhopOutMax") else 1300.0
         self.partsoutmax = p.num("PartsOutMax", True, 1.0)
         self.symmetry = p.int("Symmetry", True, 0) != 0  # JSph.cpp:714 (checks: JSph::ConfigBoundary)
+        # periodic boundaries (JSph.cpp:718-730): an axis and one offset per ?PeriodicInc? key;
+        # the two-axis keys replace everything before them and zero the offsets
+        peri = [False, False, False]
+        incs = [[0.0, 0.0, 0.0] for _ in range(3)]
         for k in ("XPeriodicIncY", "XPeriodicIncZ", "YPeriodicIncX", "YPeriodicIncZ", "ZPeriodicIncX",
-                  "ZPeriodicIncY", "XYPeriodic", "XZPeriodic", "YZPeriodic"):
+                  "ZPeriodicIncY"):
             if p.exists(k):
-                raise CaseError("Periodic boundaries are not supported by this core.")
+                ax, comp = "XYZ".index(k[0]), "XYZ".index(k[-1])
+                incs[ax][comp] = p.num(k)
+                peri[ax] = True
+        for k, axes in (("XYPeriodic", (True, True, False)), ("XZPeriodic", (True, False, True)),
+                        ("YZPeriodic", (False, True, True))):
+            if p.exists(k):
+                peri = list(axes)
+                incs = [[0.0, 0.0, 0.0] for _ in range(3)]
+        self.peri_active = int(peri[0]) | int(peri[1]) << 1 | int(peri[2]) << 2
+        self.peri_xinc, self.peri_yinc, self.peri_zinc = incs
+        if self.peri_active & 2 and self.data2d:  # JSph.cpp:730
+            raise CaseError("Cannot use periodic conditions in Y with 2D simulations")
         self.cellmode = CELLMODE_FULL   # JSphCfgRun default for the GPU (-cellmode:full)
         self.celldomfixed = False
 
@@ -1237,6 +1272,29 @@ class XmlCase:
             rows.extend(new)
         return mv
 
+    def _check_periodic_walls(self) -> None:
+        """A periodic axis closed by a boundary wall at each end (a tank with XPeriodic): the two
+        walls would face each other Dp apart through the periodic face and no particle could
+        cross.  The reference would run it; this loader refuses it as a configuration error.  A
+        wall: the first / last particle layer along the axis holds boundary particles only and
+        fills the case's whole cross-section (at least 90 % of its lattice sites), so a floor or
+        side walls that merely reach the face are none."""
+        lo, hi = self.pos.min(axis=0), self.pos.max(axis=0)
+        for ax in range(3):
+            if not self.peri_active >> ax & 1:
+                continue
+            others = [a for a in range(3) if a != ax]
+            sites = 1
+            for a in others:
+                sites *= int(round((hi[a] - lo[a]) / self.dp)) + 1
+            closed = 0
+            for layer in (self.pos[:, ax] <= lo[ax] + 0.25 * self.dp, self.pos[:, ax] >= hi[ax] - 0.25 * self.dp):
+                idx = np.flatnonzero(layer)
+                closed += int((idx < self.npb).all() and len(idx) >= 0.9 * sites)
+            if closed == 2:
+                raise CaseError(f"Periodic axis {'XYZ'[ax]} is closed by a boundary wall at each end: "
+                                "no particle can cross it.")
+
     def _check_loaded(self, h, prt):
         """JPartsLoad4::CheckConfig (JPartsLoad4.cpp:264-300)."""
         if (h["case_np"], h["case_nfixed"], h["case_nmoving"], h["case_nfloat"], h["case_nfluid"]) != (
@@ -1244,8 +1302,9 @@ class XmlCase:
             raise CaseError("Data file does not match the configuration of the case.")
         if bool(h["data2d"]) != self.data2d:
             raise CaseError("Data file does not match the dimension of the case.")
-        if h["peri_mode"] not in (0, 96):  # PERI_None, PERI_Unknown (case files)
-            raise CaseError("Data file uses periodic boundaries.")
+        # TpPeri = PeriActive (JPeriodicDef.h); PERI_Unknown (96): a case file
+        if h["peri_mode"] not in (self.peri_active, 96):
+            raise CaseError("Data file does not match the periodic configuration of the case.")
 
     # -- what the core and the PART writer read -----------------------------------------
     @property
@@ -1309,6 +1368,8 @@ class XmlCase:
             shift_coef=self.shift_coef, shift_tfs=self.shift_tfs, data2d=int(self.data2d),
             data2d_posy=self.data2d_posy, dtallparticles=self.dtallparticles, dtfixed=self.dtfixed,
             symmetry=int(self.symmetry), mdbc_corrector=int(self.mdbc_corrector),
+            peri_active=self.peri_active, peri_xinc=tuple(self.peri_xinc), peri_yinc=tuple(self.peri_yinc),
+            peri_zinc=tuple(self.peri_zinc),
         )
 
 

@@ -59,6 +59,9 @@
  *   sph_solver_set_accinputs ... JDsAccInput::RunCpu in PreInteractionVars_Forces (JSphCpu.cpp:444)
  *   sph_solver_set_damping ..... JSphCpu::RunDamping at the end of ComputeStep_Ver / _Sym
  *                                (JSphCpuSingle.cpp:683,717; JDsDamping.cpp)
+ *   SphCaseDef.peri_active ..... periodic boundaries: JSphCpuSingle::RunPeriodic before every
+ *                                divide (JSphCpuSingle.cpp:361-431), the wrap of JSphCpu::UpdatePos
+ *                                (JSphCpu.cpp:1254-1291); single domain, DBC, no bodies
  */
 #ifndef SPHCORE_H
 #define SPHCORE_H
@@ -70,7 +73,7 @@
 extern "C" {
 #endif
 
-#define SPH_ABI_VERSION 15
+#define SPH_ABI_VERSION 16
 
 typedef enum {
   SPH_OK = 0,
@@ -197,6 +200,14 @@ typedef struct SphCaseDef {
    * (JSph.cpp:1386), a particle crossing y = 0 is reflected (JSphCpu.cpp:1247) */
   int32_t symmetry;
   double dtfixed;
+  /* Periodic boundaries (JSph.cpp:718-730; RunPeriodic, JSphCpuSingle.cpp:361-431): peri_active
+   * = PeriActive (bit 1 X, 2 Y, 4 Z); peri_?inc = Peri?inc as the XML gives them (the offsets of
+   * XPeriodicIncY ...); the own-axis component is derived (-MapRealSize, JSph.cpp:2067-2069)
+   * whatever is passed.  map_realposmin/max are the REAL map (Dp/2 border on a periodic axis,
+   * JPartsLoad4.cpp:339-347); the core widens the cell map by KernelSize on each periodic axis. */
+  int32_t peri_active;
+  int32_t pad_peri;
+  double peri_xinc[3], peri_yinc[3], peri_zinc[3];
 } SphCaseDef;
 
 /*
@@ -237,6 +248,12 @@ typedef struct SphConstants {
   int32_t pad4;
   int32_t dtallparticles, symmetry; /* DtAllParticles, Symmetry            */
   double dtfixed;                   /* DtFixed (0: variable dt)             */
+  /* periodic boundaries: PeriActive, the derived Peri?inc, Map_PosMin/Max (JSph.cpp:2067-2076;
+   * all zero without a periodic axis: the map is then the real map);
+   * dom_posmin / dom_cells / dom_cellcode above follow Map_PosMin/Max */
+  int32_t peri_active, pad5;
+  double peri_xinc[3], peri_yinc[3], peri_zinc[3];
+  double map_posmin[3], map_posmax[3];
 } SphConstants;
 
 /* Step statistics kept on the device and read back on demand. */
@@ -248,12 +265,14 @@ typedef struct SphRunStats {
   uint32_t np, npb, npbok;/* current counts after the last divide           */
   uint32_t nout;          /* fluid particles excluded so far                */
   uint32_t dtmodif;       /* dt clamped to DtMin (JSphCpu.cpp:1623-1629)    */
-  uint32_t error_flags;   /* bit0: NaN/inf dt, bit1: boundary out           */
+  uint32_t error_flags;   /* bit0: NaN/inf dt, bit1: boundary out, SPH_FLAG_*  */
   float velmax, acemax, viscdtmax; /* of the last interaction              */
   float viscetadtmax;     /* NN: max effective viscosity (ViscEtaDtMax)     */
   uint64_t fused_updates; /* update launches that also classified the particles
                              for the next divide (0 with SPH_CLS_SPLIT=1, bodies,
                              motion or SPH_DIVIDE=full: the divide classifies)  */
+  uint32_t npbper, npfper;/* periodic duplicates (boundary, fluid) after the last divide;
+                             np, npb, npbok and every download count normal particles only */
 } SphRunStats;
 
 /* Host particle view (SaveData layout: JSph::SaveData, JSph.cpp:2717). */
@@ -652,6 +671,9 @@ typedef struct SphGaugeRecord {
 } SphGaugeRecord;
 /* error_flags bit of sph_solver_stats: a record found the buffer full and was dropped (not fatal) */
 #define SPH_FLAG_GAUGE_FULL 64u
+/* error_flags bit: the periodic duplicates of a divide exceeded the particle capacity (fatal:
+ * the run stops at that step, SPH_ERR_NOMEM at the next status read) */
+#define SPH_FLAG_PERIODIC_FULL 128u
 /* Configure the gauges (single domain, single phase; once, before the first step and after
  * sph_solver_set_time on a restart) with a record buffer of record_capacity records, and take
  * the measure of the current TimeStep. */
