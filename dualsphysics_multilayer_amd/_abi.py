@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-SPH_ABI_VERSION = 16
+SPH_ABI_VERSION = 17
 
 SPH_STATUS = {
     0: "SPH_OK",
@@ -36,6 +36,7 @@ _CASEDEF_DEFAULTS = {"tboundary": SPH_BOUND_DBC, "slipmode": SPH_SLIP_VEL0, "mdb
                      "peri_active": 0, "pad_peri": 0, "peri_xinc": (0.0, 0.0, 0.0), "peri_yinc": (0.0, 0.0, 0.0),
                      "peri_zinc": (0.0, 0.0, 0.0)}
 SPH_TTAB_DTFIXED, SPH_TTAB_VISCO = 0, 1
+SPH_FTMODE_NONE, SPH_FTMODE_SPH, SPH_FTMODE_EXT = 0, 1, 2  # TpFtMode (RigidAlgorithm 1 -> SPH, 0 and 2 -> EXT)
 
 
 class SphPhaseDef(C.Structure):
@@ -240,6 +241,7 @@ class SphRunStats(C.Structure):
         ("fused_updates", C.c_uint64),
         ("npbper", C.c_uint32),
         ("npfper", C.c_uint32),
+        ("dem_dtforce", C.c_double),
     ]
 
     def as_dict(self) -> dict:
@@ -340,6 +342,7 @@ class SphPartHeader(C.Structure):
         ("gravity", C.c_float * 3),
         ("mkbound", C.c_uint32),
         ("mkfluid", C.c_uint32),
+        ("dem_dtforce", C.c_double),
     ]
 
     def as_dict(self) -> dict:
@@ -579,6 +582,26 @@ def floating_array(floatings: list):
     return arr
 
 
+class SphDemDef(C.Structure):
+    """StDemData of one boundary block (JSph::LoadDemData), by its particle code."""
+    _fields_ = [
+        ("code", C.c_uint32),
+        ("mass", C.c_float),
+        ("massp", C.c_float),
+        ("tau", C.c_float),
+        ("kfric", C.c_float),
+        ("restitu", C.c_float),
+    ]
+
+
+def dem_array(demdata: list):
+    arr = (SphDemDef * max(1, len(demdata)))()
+    for i, d in enumerate(demdata):
+        for name, _ in SphDemDef._fields_:
+            setattr(arr[i], name, d[name])
+    return arr
+
+
 class HostParticles:
     """Owns numpy arrays and exposes them as an SphParticlesHost view."""
 
@@ -628,4 +651,5 @@ def check_struct_sizes() -> dict:
         "SphAccInputDef": C.sizeof(SphAccInputDef),
         "SphDampingDef": C.sizeof(SphDampingDef),
         "SphDampingDerived": C.sizeof(SphDampingDerived),
+        "SphDemDef": C.sizeof(SphDemDef),
     }

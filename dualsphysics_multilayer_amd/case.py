@@ -796,3 +796,168 @@ class PeriodicChannelCase:
                    peri_mode=96, pos_double=1)
         write_part(path + ".bi4", hdr, dict(idp=self.idp, pos=self.pos, vel=self.vel, rhop=self.rhop))
         return path
+
+
+@dataclass
+class BlocksCase:
+    """A tank (floor and side walls) with a shallow pool at one end and three floating boxes of
+    different materials over the dry part of the floor, for the DEM collisions of RigidAlgorithm=2
+    (and the collision-free RigidAlgorithm=0): box 0 is dropped onto the floor, box 1 is thrown at
+    box 2, which rests above the floor.  Written out as ``Case<name>.xml`` + ``.bi4`` + the
+    property file ``Blocks_Materials.xml`` for any solver that loads DualSPHysics cases.
+
+    Lattice (i, j, k) dp: floor k = 0, walls i = 0, i = nx - 1 (3-D: j = 0, j = ny - 1) up to
+    k = nz; pool i in [1, pool], k in [1, depth]; boxes of `side`^3 (2-D: `side`^2 in the plane
+    y = 0) particles, the lowest layer `gap` dp above the floor, box 1 `gap` dp beside box 2."""
+
+    dp: float = 0.02
+    nx: int = 26
+    ny: int = 11
+    nz: int = 7
+    pool: int = 8
+    depth: int = 3
+    side: int = 3
+    gap: float = 1.2
+    data2d: bool = False
+    rigidalgorithm: int = 2
+    step_algorithm: int = STEP_VERLET
+    tdensity: int = DDT_DDT2
+    ddtvalue: float = 0.1
+    visco: float = 0.1
+    cflnumber: float = 0.2
+    coefsound: float = 20.0
+    gravity: tuple = (0.0, 0.0, -9.81)
+    rhop0: float = 1000.0
+    gamma: float = 7.0
+    young: float = 2.0e6
+    rho_body: tuple = (600.0, 900.0, 1400.0)
+    velini: tuple = ((0.0, 0.0, -2.0), (2.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+    timemax: float = 1.0
+    timeout: float = 0.01
+
+    def __post_init__(self) -> None:
+        dp, s = self.dp, self.side
+        js = np.arange(1) if self.data2d else np.arange(self.ny)
+        k, j, i = np.meshgrid(np.arange(self.nz + 1), js, np.arange(self.nx), indexing="ij")
+        wall = (k == 0) | (i == 0) | (i == self.nx - 1)
+        if not self.data2d:
+            wall |= (j == 0) | (j == self.ny - 1)
+        fixed = np.stack([i[wall], j[wall], k[wall]], axis=1).astype(np.float64)
+        fj = js if self.data2d else js[1:-1]
+        fk, fjj, fi = np.meshgrid(np.arange(1, self.depth + 1), fj, np.arange(1, self.pool + 1), indexing="ij")
+        fluid = np.stack([fi.ravel(), fjj.ravel(), fk.ravel()], axis=1).astype(np.float64)
+        jm = 0.0 if self.data2d else float((self.ny - s) // 2)
+        bj = np.arange(1) if self.data2d else np.arange(s)
+        bk, bjj, bi = np.meshgrid(np.arange(s), bj, np.arange(s), indexing="ij")
+        box = np.stack([bi.ravel(), bjj.ravel(), bk.ravel()], axis=1).astype(np.float64)
+        x0 = float(self.pool + 4)
+        x2 = x0 + s + 4.0
+        x1 = x2 - (s - 1) - self.gap
+        org = [(x0, jm, self.gap), (x1, jm, 3.0), (x2, jm, 3.0)]
+        self.boxes = [box + np.array(o) for o in org]
+        lat = np.concatenate([fixed] + self.boxes + [fluid])
+        self.pos = lat * dp
+        self.nfixed = len(fixed)
+        self.npb = self.nfixed
+        self.np = len(lat)
+        self.idp = np.arange(self.np, dtype=np.uint32)
+        self.vel = np.zeros((self.np, 3), np.float32)
+        o = self.nfixed
+        for b, v in zip(self.boxes, self.velini):
+            self.vel[o:o + len(b)] = np.asarray(v, np.float32)
+            o += len(b)
+        self.nfloat = o - self.nfixed
+        g, rho0, gamma = -self.gravity[2], self.rhop0, self.gamma
+        hswl = self.depth * dp
+        cs0 = self.coefsound * math.sqrt(g * hswl)
+        self._b = cs0 * cs0 * rho0 / gamma
+        dim = 2 if self.data2d else 3
+        self._h = math.sqrt(dim * dp * dp)
+        self._mass = rho0 * dp ** dim
+        rhop = np.full(self.np, np.float32(rho0), np.float32)
+        z = self.pos[o:, 2]
+        rhop[o:] = (rho0 * np.power(1.0 + rho0 * g * (hswl - z) / self._b, 1.0 / gamma)).astype(np.float32)
+        self.rhop = rhop
+
+    MATERIALS = (("tank", 4.0, 0.30, 0.45, 0.70), ("wood", 1.0, 0.35, 0.40, 0.80), ("pvc", 2.0, 0.30, 0.25, 0.60),
+                 ("lead", 0.5, 0.40, 0.60, 0.50))  # name, Young / `young`, Poisson, Kfric, Restitution
+
+    def _property(self, m) -> str:
+        return ('<property name="%s">\n<Young_Modulus value="%.10g"/>\n<PoissonRatio value="%.10g"/>\n'
+                '<Kfric value="%.10g"/>\n<Restitution_Coefficient value="%.10g"/>\n</property>\n'
+                % (m[0], m[1] * self.young, m[2], m[3], m[4]))
+
+    def materials_xml(self) -> str:
+        """Blocks_Materials.xml: the materials of boxes 1 and 2 (a <propertyfile>)."""
+        return ('<?xml version="1.0" encoding="UTF-8" ?>\n<materials>\n' + self._property(self.MATERIALS[2]) +
+                self._property(self.MATERIALS[3]) + "</materials>\n")
+
+    def xml(self, app: str = "dualsphysics_multilayer_amd") -> str:
+        dp, dim = self.dp, (2 if self.data2d else 3)
+        par = [("StepAlgorithm", self.step_algorithm), ("VerletSteps", 40), ("Kernel", 2), ("ViscoTreatment", 1),
+               ("Visco", "%.10g" % self.visco), ("ViscoBoundFactor", 1), ("DensityDT", self.tdensity),
+               ("DensityDTvalue", "%.10g" % self.ddtvalue), ("Shifting", 0), ("RigidAlgorithm", self.rigidalgorithm),
+               ("FtPause", 0), ("CoefDtMin", 0.05), ("DtIni", 0), ("DtMin", 0), ("TimeMax", "%.10g" % self.timemax),
+               ("TimeOut", "%.10g" % self.timeout), ("PartsOutMax", 1), ("RhopOutMin", 700), ("RhopOutMax", 1300)]
+        lines = ['<?xml version="1.0" encoding="UTF-8" ?>', '<case app="%s">' % app, "<execution>", "<constants>",
+                 '<data2d value="%s"/>' % ("true" if self.data2d else "false")]
+        if self.data2d:
+            lines.append('<data2dposy value="0"/>')
+        lines += ['<gravity x="%.10g" y="%.10g" z="%.10g"/>' % tuple(self.gravity),
+                  '<cflnumber value="%.10g"/>' % self.cflnumber, '<gamma value="%.10g"/>' % self.gamma,
+                  '<rhop0 value="%.10g"/>' % self.rhop0, '<dp value="%.10g"/>' % dp, '<h value="%.10E"/>' % self._h,
+                  '<b value="%.10E"/>' % self._b, '<massbound value="%.10E"/>' % self._mass,
+                  '<massfluid value="%.10E"/>' % self._mass, "</constants>",
+                  '<particles np="%d" nb="%d" nbf="%d" mkboundfirst="10" mkfluidfirst="0">'
+                  % (self.np, self.nfixed + self.nfloat, self.nfixed),
+                  '<fixed mkbound="0" mk="10" begin="0" count="%d" property="tank"/>' % self.nfixed]
+        o = self.nfixed
+        names = ("wood", "pvc", "lead")
+        for c, b in enumerate(self.boxes):
+            n = len(b)
+            massp = self.rho_body[c] * dp ** dim
+            mass = massp * n
+            cen = self.pos[o:o + n].mean(axis=0)
+            a2 = (self.side * dp) ** 2
+            ine = mass * a2 / 6.0
+            lines += ['<floating mkbound="%d" mk="%d" begin="%d" count="%d" property="%s">' % (c + 1, c + 11, o, n, names[c]),
+                      '<massbody value="%.10g"/>' % mass, '<masspart value="%.10g"/>' % massp,
+                      '<center x="%.10g" y="%.10g" z="%.10g"/>' % tuple(cen),
+                      '<inertia x="%.10g" y="%.10g" z="%.10g"/>' % (ine, ine, ine)]
+            if any(self.velini[c]):
+                lines.append('<linearvelini x="%.10g" y="%.10g" z="%.10g"/>' % tuple(self.velini[c]))
+            lines.append("</floating>")
+            o += n
+        lines += ['<fluid mkfluid="0" mk="0" begin="%d" count="%d"/>' % (o, self.np - o),
+                  "<properties>", "<links>", '<link mk="10" property="tank"/>', '<link mk="11" property="wood"/>',
+                  '<link mk="12" property="pvc"/>', '<link mk="13" property="lead"/>', "</links>",
+                  self._property(self.MATERIALS[0]) + self._property(self.MATERIALS[1]) +
+                  '<propertyfile file="Blocks_Materials.xml" path="materials"/>', "</properties>", "</particles>",
+                  "<parameters>"]
+        lines += ['<parameter key="%s" value="%s"/>' % kv for kv in par]
+        lines += ['<simulationdomain><posmin x="default" y="default" z="default"/>'
+                  '<posmax x="default" y="default" z="default + 50%"/></simulationdomain>',
+                  "</parameters>", "</execution>", "</case>", ""]
+        return "\n".join(lines)
+
+    def write(self, dirname: str, name: str = "CaseBlocks") -> str:
+        """Case<name>.xml, .bi4 and Blocks_Materials.xml into dirname; returns the case path."""
+        import os
+
+        from .core import write_part
+
+        path = os.path.join(dirname, name)
+        with open(path + ".xml", "w") as f:
+            f.write(self.xml())
+        with open(os.path.join(dirname, "Blocks_Materials.xml"), "w") as f:
+            f.write(self.materials_xml())
+        h = float(np.float32(float("%.10E" % self._h)))
+        hdr = dict(app_name="dualsphysics_multilayer_amd", case_name=name, cpart=0, npok=self.np, nout=0, step=0,
+                   timestep=0.0, case_np=self.np, case_nfixed=self.nfixed, case_nfloat=self.nfloat,
+                   case_nfluid=self.np - self.nfixed - self.nfloat, dp=float("%.10g" % self.dp), h=h,
+                   b=float("%.10E" % self._b), rhop0=self.rhop0, gamma=self.gamma, massbound=float("%.10E" % self._mass),
+                   massfluid=float("%.10E" % self._mass), case_posmin=self.pos.min(axis=0).tolist(),
+                   case_posmax=self.pos.max(axis=0).tolist(), data2d=int(self.data2d), data2d_posy=0.0,
+                   peri_mode=96, pos_double=1)
+        write_part(path + ".bi4", hdr, dict(idp=self.idp, pos=self.pos, vel=self.vel, rhop=self.rhop))
+        return path

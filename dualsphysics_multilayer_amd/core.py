@@ -18,6 +18,8 @@ import numpy as np
 
 from ._abi import (
     SPH_ABI_VERSION,
+    SPH_FTMODE_EXT,
+    SPH_FTMODE_SPH,
     SPH_TTAB_DTFIXED,
     SPH_TTAB_VISCO,
     SPH_STATUS,
@@ -29,6 +31,7 @@ from ._abi import (
     SphPartHeader,
     SphSlabDef,
     SphSlabInfo,
+    SphDemDef,
     SphFloatingDef,
     SphFloatingState,
     SphGaugeDef,
@@ -44,6 +47,7 @@ from ._abi import (
     SphMotionEvent,
     SphMotionMov,
     SphMotionObj,
+    dem_array,
     floating_array,
     motion_arrays,
     motion_tree_arrays,
@@ -101,6 +105,7 @@ EXPORTED_SYMBOLS = (
     "sph_solver_set_motion",
     "sph_solver_set_motion_tree",
     "sph_solver_set_floatings",
+    "sph_solver_set_rigid",
     "sph_solver_set_floating_table",
     "sph_solver_set_time_table",
     "sph_solver_floatings",
@@ -196,7 +201,8 @@ def load_library(path: str = LIB_PATH):
     L.sph_solver_set_floating_table.argtypes = [vp, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double)]
     L.sph_solver_floatings.argtypes = [vp, C.c_uint32, C.POINTER(SphFloatingState), C.POINTER(C.c_uint32)]
-    L.sph_partfloat_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32] + [vp] * 6 + [C.c_uint32] + [vp] * 8
+    L.sph_partfloat_write.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32] + [vp] * 6 + [C.c_uint32] + [vp] * 9
+    L.sph_solver_set_rigid.argtypes = [vp, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(SphDemDef), C.c_double]
     L.sph_partfloat_read.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     L.sph_extra_normals_read.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_int32)]
@@ -321,6 +327,17 @@ class SphGpuSingle:
                     dp = C.POINTER(C.c_double)
                     _check(L.sph_solver_set_floating_table(self._h, b, kind, len(rows), t.ctypes.data_as(dp),
                                                            v.ctypes.data_as(dp)))
+            # RigidAlgorithm 0 / 2: FTMODE_Ext and the DEM data of the boundary blocks
+            if getattr(case, "ftmode", SPH_FTMODE_SPH) == SPH_FTMODE_EXT:
+                self.set_rigid(SPH_FTMODE_EXT, getattr(case, "use_dem", False), getattr(case, "demdata", []),
+                               getattr(case, "demdtforce0", 0.0))
+
+    def set_rigid(self, ftmode: int, use_dem: bool = False, demdata: list = (), demdtforce: float = 0.0) -> None:
+        """The floating bodies' rigid algorithm (SPH_FTMODE_*; XmlCase.demdata dicts: code, mass, massp,
+        tau, kfric, restitu); once, after the bodies and before the first step."""
+        arr = dem_array(demdata)
+        _check(load_library().sph_solver_set_rigid(self._h, int(ftmode), int(bool(use_dem)), len(demdata), arr,
+                                                   float(demdtforce)))
 
     def set_accinputs(self, accinputs: list) -> None:
         """Imposed accelerations (XmlCase.accinputs dicts: code1, code2, globalgravity, timestart,
@@ -711,6 +728,7 @@ def part_header(case, stats: dict | None = None, cpart: int = 0, app_name: str =
     return dict(app_name=app_name, case_name=case_name, cpart=cpart, nout=int(st.get("nout", 0)),
                 step=int(st.get("nstep", 0)), timestep=float(st.get("time", 0.0)),
                 symplectic_dtpre=float(st.get("sym_dtpre", 0.0)) if case.step_algorithm == 2 else 0.0,
+                dem_dtforce=float(st.get("dem_dtforce", 0.0)),
                 domain_min=list(k["map_realposmin"]),
                 domain_max=[k["map_realposmin"][i] + k["map_realsize"][i] for i in range(3)],
                 case_np=case.np, case_nfixed=case.npb, case_nfluid=case.np - case.npb,
@@ -737,6 +755,7 @@ def write_partfloat(path: str, floatings: list, parts: list, mkboundfirst: int =
     cp = u32([p["cpart"] for p in parts])
     st = u32([p["step"] for p in parts])
     ts = np.ascontiguousarray([p["time"] for p in parts], np.float64)
+    dem = np.ascontiguousarray([p.get("demdtforce", 0.0) for p in parts], np.float64)
     cen = np.ascontiguousarray([[b["center"] for b in p["bodies"]] for p in parts], np.float64).reshape(-1)
     arr = {k: f32([[b[k] for b in p["bodies"]] for p in parts]).reshape(-1)
            for k in ("fvel", "fomega", "facelin", "faceang")}
@@ -744,7 +763,7 @@ def write_partfloat(path: str, floatings: list, parts: list, mkboundfirst: int =
     _check(load_library().sph_partfloat_write(path.encode(), app.encode(), mkboundfirst, nft,
                                               *[ptr(a) for a in head], len(parts), ptr(cp), ptr(st), ptr(ts),
                                               ptr(cen), *[ptr(arr[k]) for k in ("fvel", "fomega", "facelin",
-                                                                                "faceang")]))
+                                                                                "faceang")], ptr(dem)))
 
 
 # ---- restart of floating bodies and mDBC (JSphCpu::InitFloating, JDsExtraData) -----------

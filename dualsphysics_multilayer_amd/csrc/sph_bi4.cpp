@@ -335,6 +335,7 @@ void part_read(const std::string& path, SphPartHeader& h, SphParticlesHost* out)
   part->get_double3("DomainMin", h.domain_min);
   part->get_double3("DomainMax", h.domain_max);
   h.symplectic_dtpre = part->get_double("SymplecticDtPre", 0);
+  h.dem_dtforce = part->get_double("DemDtForce", 0);
   h.np_total = part->get_uint("NpTotal", 0);
   h.case_np = root.get_uint("CaseNp", 0);
   h.case_nfixed = root.get_uint("CaseNfixed", 0);
@@ -445,6 +446,7 @@ void part_write(const std::string& path, const SphPartHeader& h, const SphPartic
   part.set("DomainMax", bi4::Double3, h.domain_max, 24);
   if (h.np_total) part.set_pod("NpTotal", bi4::Ullong, uint64_t(h.np_total));
   if (h.symplectic_dtpre > 0) part.set_pod("SymplecticDtPre", bi4::Double, h.symplectic_dtpre);
+  if (h.dem_dtforce > 0) part.set_pod("DemDtForce", bi4::Double, h.dem_dtforce);  // UseDEM (JSph.cpp:2597)
   const uint32_t n = h.npok;
   part.add_array("Idp", bi4::Uint, n, p.idp);
   if (h.pos_double) {
@@ -571,7 +573,7 @@ void partfloat_write(const std::string& path, const char* app, uint32_t mkboundf
                      const uint16_t* mkbound, const uint32_t* begin, const uint32_t* count, const float* mass,
                      const float* massp, const float* radius, uint32_t nparts, const uint32_t* cpart,
                      const uint32_t* step, const double* timestep, const double* center, const float* fvel,
-                     const float* fomega, const float* facelin, const float* faceang) {
+                     const float* fomega, const float* facelin, const float* faceang, const double* demdtforce) {
   bi4::Item head;
   head.name = "JPartFloatBi4";  // the loader finds it as LS0000_JPartFloatBi4 (JPartFloatBi4.cpp:531)
   head.set_text("AppName", app ? app : "");
@@ -594,7 +596,7 @@ void partfloat_write(const std::string& path, const char* app, uint32_t mkboundf
     it.set_pod("Cpart", bi4::Uint, cpart[k]);
     it.set_pod("Step", bi4::Uint, step[k]);
     it.set_pod("TimeStep", bi4::Double, timestep[k]);
-    it.set_pod("DemDtForce", bi4::Double, 0.0);
+    it.set_pod("DemDtForce", bi4::Double, demdtforce ? demdtforce[k] : 0.0);  // JSph.cpp:2705
     it.add_array("center", bi4::Double3, nft, center + size_t(3) * nft * k);
     it.add_array("fvel", bi4::Float3, nft, fvel + size_t(3) * nft * k);
     it.add_array("fomega", bi4::Float3, nft, fomega + size_t(3) * nft * k);

@@ -15,7 +15,7 @@
 //   mvrectfile (mvfile, mvpredef), mvrotfile, mvnull, flash movements (negative duration),
 //   chained by `next`, started by <begin> events (finish optional), in a tree of nested
 //   <obj> / <objreal> objects (a parent's motion moves its children and their axes).
-// * Floating bodies (RigidAlgorithm=1, SPH).  JSphCpuSingle::RunFloating
+// * Floating bodies (RigidAlgorithm=1, SPH; 0 and 2 differ in Interaction_Forces only: sph_dem.hip).  JSphCpuSingle::RunFloating
 //   (JSphCpuSingle.cpp:897-1010): FtCalcForcesSum (:748-768), FtCalcForces (:775-815),
 //   FtCalcForcesRes (:822-858), constraints (:863-873), then the particle update and the
 //   body state.  GPU twins: cusph::FtCalcForcesSum/FtCalcForces/FtUpdate

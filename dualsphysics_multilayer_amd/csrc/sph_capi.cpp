@@ -184,6 +184,12 @@ int sph_solver_measure(SphSolver* s, SphGaugeRecord* out, uint32_t n) {
   NOT_MEMBER(s);
   return guard([&] { s->impl->Measure(out, n); });
 }
+int sph_solver_set_rigid(SphSolver* s, int32_t ftmode, int32_t use_dem, uint32_t ndem, const SphDemDef* dem,
+                         double demdtforce) {
+  NEED(s && (dem || !ndem));
+  return guard([&] { s->impl->SetRigid(ftmode, use_dem != 0, ndem, dem, demdtforce); });
+}
+
 int sph_solver_set_accinputs(SphSolver* s, uint32_t n, const SphAccInputDef* defs, uint32_t nrows, const double* rows) {
   NEED(s && defs && n && (rows || !nrows));
   return guard([&] { s->impl->SetAccInputs(n, defs, nrows, rows); });
@@ -223,12 +229,13 @@ int sph_partfloat_write(const char* path, const char* app, uint32_t mkboundfirst
                         const uint16_t* mkbound, const uint32_t* begin, const uint32_t* count, const float* mass,
                         const float* massp, const float* radius, uint32_t nparts, const uint32_t* cpart,
                         const uint32_t* step, const double* timestep, const double* center, const float* fvel,
-                        const float* fomega, const float* facelin, const float* faceang) {
+                        const float* fomega, const float* facelin, const float* faceang,
+                        const double* demdtforce) {
   NEED(path && nft && mkbound && begin && count && mass && massp && radius && (!nparts || (cpart && step &&
        timestep && center && fvel && fomega && facelin && faceang)));
   return guard([&] {
     sphx::partfloat_write(path, app, mkboundfirst, nft, mkbound, begin, count, mass, massp, radius, nparts, cpart,
-                          step, timestep, center, fvel, fomega, facelin, faceang);
+                          step, timestep, center, fvel, fomega, facelin, faceang, demdtforce);
   });
 }
 int sph_partfloat_read(const char* path, uint32_t cpart, uint32_t nft, double* center, float* fvel, float* fomega,

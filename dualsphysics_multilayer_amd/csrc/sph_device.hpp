@@ -218,6 +218,10 @@ struct DevScalars {
   unsigned red[4][64];
   // periodic boundaries (sph_periodic.hip): duplicates after the last RunPeriodic, by type
   unsigned npbper, npfper;
+  // DEM (sph_dem.hip): DemDtForce, the dt of the tangential spring.  Verlet: the last step's dt
+  // (JSphCpuSingle.cpp:678; DtIni before the first, a restart's PART value); Symplectic: the
+  // interactions take dt/2 and dt of the step in flight (:700,709) and this holds dt after it.
+  double demdtforce;
 };
 // RED_VISCETA: NN max effective viscosity (ViscEtaDtMax, JSphCpuSingle.cpp:633 in the v5.0 solver)
 constexpr int RED_VELMAX2 = 0, RED_ACEMAX2 = 1, RED_VISCDT = 2, RED_VISCETA = 3, RED_SLOTS = 64;

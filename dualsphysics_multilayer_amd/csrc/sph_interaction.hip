@@ -47,11 +47,16 @@ struct FtView {
   const float* massp;  // per floating body
 };
 
-template <int TDENSITY, bool BOUNDP2, bool FT = false>
+// EXT (FTMODE_Ext, RigidAlgorithm 0 and 2; p1ext = p1 is floating): a floating p1 computes no
+// pair with a floating p2 (its bound pass is not run at all), JSphCpu.cpp:705; every term the
+// `compute` flag leaves unguarded there is already off for a floating p1 (DDT) or refused
+// (shifting, Laminar+SPS).
+template <int TDENSITY, bool BOUNDP2, bool FT = false, bool EXT = false>
 __device__ __forceinline__ void fluid_cell(const KConst& K, float rx, float ry, float rz, float4 vr1, float pr1,
                                            unsigned pini, unsigned pfin, const float4* __restrict__ poscell,
                                            const float4* __restrict__ velrhop, const float* __restrict__ press,
-                                           float massp2c, float visco, Acc& a, FtView ft = {}) {
+                                           float massp2c, float visco, Acc& a, FtView ft = {},
+                                           bool p1ext = false) {
   for (unsigned p2 = pini; p2 < pfin; p2++) {
     const float4 pc2 = poscell[p2];
     const float drx = rx - pc2.x, dry = ry - pc2.y, drz = rz - pc2.z;
@@ -63,6 +68,7 @@ __device__ __forceinline__ void fluid_cell(const KConst& K, float rx, float ry, 
         const typecode c2 = ft.code[p2];
         ftp2 = CodeType(c2) == CODE_TYPE_FLOATING;
         if (ftp2) {
+          if (EXT && p1ext) continue;
           massp2 = ft.massp[c2 & CODE_MASKVALUE];
           if (TDENSITY == 1 && massp2 <= K.massfluid * 1.2f) a.delta = FLT_MAX;
         }
@@ -134,12 +140,12 @@ __device__ __forceinline__ Range3 ngs_range(int cx, int cy, int cz, const DivGri
   return r;
 }
 
-template <int TDENSITY, bool BOUNDP2, bool FT = false>
+template <int TDENSITY, bool BOUNDP2, bool FT = false, bool EXT = false>
 __device__ __forceinline__ void fluid_pass(const KConst& K, const DivGrid& g, const unsigned* __restrict__ begincell,
                                            const float4 pc1, int cx, int cy, int cz, const Range3& rg, float4 vr1,
                                            float pr1, const float4* __restrict__ poscell,
                                            const float4* __restrict__ velrhop, const float* __restrict__ press, Acc& a,
-                                           FtView ft = {}) {
+                                           FtView ft = {}, bool p1ext = false) {
   const unsigned cellinit = (BOUNDP2 ? 0u : g.boxfluid);
   const float massp2 = (BOUNDP2 ? K.massbound : K.massfluid);
   const float visco = (BOUNDP2 ? K.viscobound : K.visco);
@@ -152,15 +158,15 @@ __device__ __forceinline__ void fluid_pass(const KConst& K, const DivGrid& g, co
       for (int x = rg.xi; x < rg.xf; x++) {
         const unsigned pfin = begincell[row + x + 1];
         const float rx = pc1.x + float(cx - x) * K.scell;
-        fluid_cell<TDENSITY, BOUNDP2, FT>(K, rx, ry, rz, vr1, pr1, pini, pfin, poscell, velrhop, press, massp2, visco, a,
-                                          ft);
+        fluid_cell<TDENSITY, BOUNDP2, FT, EXT>(K, rx, ry, rz, vr1, pr1, pini, pfin, poscell, velrhop, press, massp2, visco,
+                                               a, ft, p1ext);
         pini = pfin;
       }
     }
   }
 }
 
-template <int TDENSITY, bool ONLYBOUND = false, bool FT = false>
+template <int TDENSITY, bool ONLYBOUND = false, bool FT = false, bool EXT = false>
 __global__ __launch_bounds__(256) void k_interaction(DevScalars* __restrict__ sc, const float4* __restrict__ poscell,
                                                      const float4* __restrict__ velrhop,
                                                      const float* __restrict__ press,
@@ -188,9 +194,12 @@ __global__ __launch_bounds__(256) void k_interaction(DevScalars* __restrict__ sc
       Acc f = {0, 0, 0, 0, 0, 0};
       Acc b = {0, 0, 0, 0, 0, 0};
       // a floating p1 gets no DDT (JSphCpu.cpp:659-662): both passes start sticky
-      if (FT && TDENSITY && CodeType(ft.code[p1]) == CODE_TYPE_FLOATING) f.delta = b.delta = FLT_MAX;
-      fluid_pass<TDENSITY, false, FT>(K, g, begincell, pc1, cx, cy, cz, rg, vr1, pr1, poscell, velrhop, press, f, ft);
-      fluid_pass<TDENSITY, true, FT>(K, g, begincell, pc1, cx, cy, cz, rg, vr1, pr1, poscell, velrhop, press, b, ft);
+      const bool ftp1 = FT && CodeType(ft.code[p1]) == CODE_TYPE_FLOATING;
+      if (FT && TDENSITY && ftp1) f.delta = b.delta = FLT_MAX;
+      fluid_pass<TDENSITY, false, FT, EXT>(K, g, begincell, pc1, cx, cy, cz, rg, vr1, pr1, poscell, velrhop, press, f, ft,
+                                           ftp1);
+      if (!(EXT && ftp1))  // FTMODE_Ext: no floating - bound pair (JSphCpu.cpp:705)
+        fluid_pass<TDENSITY, true, FT, EXT>(K, g, begincell, pc1, cx, cy, cz, rg, vr1, pr1, poscell, velrhop, press, b, ft);
       // Store exactly as the two CPU passes do (JSphCpu.cpp:800-818).
       float ar = 0.f, ax = 0.f, ay = 0.f, az = 0.f, delta = 0.f;
       if (f.ar != 0.f || f.ax != 0.f || f.ay != 0.f || f.az != 0.f || f.visc != 0.f) {
@@ -237,7 +246,10 @@ __global__ __launch_bounds__(256) void k_interaction(DevScalars* __restrict__ sc
                   float massp2 = K.massfluid;  // JSphCpu.cpp:589-594
                   if (FT) {
                     const typecode c2 = ft.code[p2];
-                    if (CodeType(c2) == CODE_TYPE_FLOATING) massp2 = ft.massp[c2 & CODE_MASKVALUE];
+                    if (CodeType(c2) == CODE_TYPE_FLOATING) {
+                      if (EXT) continue;  // FTMODE_Ext: no bound - floating pair (JSphCpu.cpp:594)
+                      massp2 = ft.massp[c2 & CODE_MASKVALUE];
+                    }
                   }
                   arp1 += massp2 * (dvx * frx + dvy * fry + dvz * frz) * (vr1.w / vr2.w);
                   const float dot = drx * dvx + dry * dvy + drz * dvz;
@@ -260,8 +272,18 @@ __global__ __launch_bounds__(256) void k_interaction(DevScalars* __restrict__ sc
 
 void launch_interaction(hipStream_t stm, unsigned cap, DevScalars* sc, const float4* poscell, const float4* velrhop,
                         const float* press, const unsigned* begincell, DivGrid g, const KConst& K, float4* arace,
-                        const typecode* code, const float* ftmassp) {
+                        const typecode* code, const float* ftmassp, bool ftext) {
   const unsigned nb = (cap + 255) / 256;
+  if (ftmassp && ftext) {
+    const FtView ft = {code, ftmassp};
+    switch (K.tdensity) {
+      case 0: hipLaunchKernelGGL((k_interaction<0, false, true, true>), dim3(nb), dim3(256), 0, stm, sc, poscell, velrhop, press, begincell, g, K, arace, ft); break;
+      case 1: hipLaunchKernelGGL((k_interaction<1, false, true, true>), dim3(nb), dim3(256), 0, stm, sc, poscell, velrhop, press, begincell, g, K, arace, ft); break;
+      case 2: hipLaunchKernelGGL((k_interaction<2, false, true, true>), dim3(nb), dim3(256), 0, stm, sc, poscell, velrhop, press, begincell, g, K, arace, ft); break;
+      default: hipLaunchKernelGGL((k_interaction<3, false, true, true>), dim3(nb), dim3(256), 0, stm, sc, poscell, velrhop, press, begincell, g, K, arace, ft); break;
+    }
+    return;
+  }
   if (ftmassp) {
     const FtView ft = {code, ftmassp};
     switch (K.tdensity) {

@@ -99,6 +99,7 @@ struct P1 {
   float x, y, z;        // x relative to the item's x origin, y/z cell-relative
   float4 vr;            // velocity, rho
   float press, inv_rho; // pressure (0 for a boundary p1), 1/rho
+  bool ext;             // FTMODE_Ext instantiations (TDENSITY | 32): p1 is a floating particle
 };
 
 // Per-pass constants.  The pair body accumulates sums with the per-pass factors
@@ -159,6 +160,12 @@ __device__ __forceinline__ void pair_body(const KConst& K, const P1& p, float dr
                                           bool ok, const float4& B, const CR& C, const PassK& Q, TAcc& a) {
   constexpr int TD = TDENSITY & 7;  // DDT mode; bit 3: the Fourtakas term as its series (K.ddtseries)
   constexpr bool CUB = (TDENSITY & 16) != 0;  // bit 4: the Cubic spline kernel
+  // bit 5: FTMODE_Ext (RigidAlgorithm 0 and 2; FT records).  A bound p1 skips a floating p2, a
+  // floating p1 skips a floating p2 (its bound pass runs on a p1 out of reach, fluid_tiled):
+  // the `compute` flag of JSphCpu.cpp:594,705.  A skipped pair is a pair out of reach: kernel
+  // factor 0 and ok false, so every sum gets +0 and neither visc nor the DDT stop sees it (the
+  // terms the flag leaves unguarded are off for a floating p1, or refused: shifting, SPS).
+  constexpr bool EXT = (TDENSITY & 32) != 0;
   const float rad = fsqrt_(rr2);
   float w3, wqc = 0.f, qc = 0.f;
   if (CUB) {
@@ -175,6 +182,10 @@ __device__ __forceinline__ void pair_body(const KConst& K, const P1& p, float dr
     // so the kernel factor needs no pair test
     const float wq = __builtin_amdgcn_fmed3f(fmaf(K.mhalfovh, rad, 1.f), 0.f, 1.f);
     w3 = wq * wq * wq;
+  }
+  if (EXT && FT && MODE != 1 && (MODE == 2 || p.ext) && crec_kind(C) != 0.f) {
+    w3 = 0.f;
+    ok = false;
   }
   const float dvx = p.vr.x - B.x, dvy = p.vr.y - B.y, dvz = p.vr.z - B.z;
   const float dot = drx * dvx + dry * dvy + drz * dvz;
@@ -717,6 +728,7 @@ __device__ __forceinline__ void fluid_tiled(DevScalars* __restrict__ sc, const u
                                             float4* __restrict__ arace, const FtRec& ft) {
   constexpr int tcap = TcapT<FT>::v;
   constexpr int TD = TDENSITY & 7;
+  constexpr bool EXT = (TDENSITY & 32) != 0;  // FTMODE_Ext (pair_body)
   // position records then velrhop records in ONE array: the candidate test's last group of
   // 32 may read up to 31 records past a window that ends at tcap, which stays inside it
   __shared__ float4 sAB[2 * tcap];
@@ -775,6 +787,7 @@ __device__ __forceinline__ void fluid_tiled(DevScalars* __restrict__ sc, const u
         p.press = 0.f;
       }
       p.inv_rho = frcp(p.vr.w);
+      p.ext = false;
       const int lxa = max(cx1 - S, 0), lxb = min(cx1 + S, g.ncx - 1);
       const float thr = K.kernelsize2 * 1.0001f - (p.x * p.x + p.y * p.y + p.z * p.z);
       const RowCtx rc{cy, cz, xa, xb, lxa, lxb, xo, act, p1};
@@ -787,10 +800,21 @@ __device__ __forceinline__ void fluid_tiled(DevScalars* __restrict__ sc, const u
       } else {
         // a floating p1 gets no DDT (JSphCpu.cpp:659-662)
         const bool ftp1 = FT && act && CodeType(ft.code[p1]) == CODE_TYPE_FLOATING;
+        if (EXT) p.ext = ftp1;
         f = pass_s<TDENSITY, 0, FT, S>(K, g, rc, p, thr, pass_k(K, cvisc_f, K.massfluid, p.vr.w), bc, poscell,
                                        velrhop, press, sA, sB, sC, ft, ftp1);
-        bnd = pass_s<TDENSITY, 1, FT, S>(K, g, rc, p, thr, pass_k(K, cvisc_b, K.massbound, p.vr.w), bc, poscell,
-                                         velrhop, press, sA, sB, sC, ft, ftp1);
+        if (EXT) {
+          // FTMODE_Ext: a floating p1 has no pair with a bound p2 (JSphCpu.cpp:705): its lane walks
+          // the bound rows as an idle lane does, from a position no record reaches
+          P1 pb = p;
+          if (ftp1) pb.x = pb.y = pb.z = 1e30f;
+          const float thrb = K.kernelsize2 * 1.0001f - (pb.x * pb.x + pb.y * pb.y + pb.z * pb.z);
+          bnd = pass_s<TDENSITY, 1, FT, S>(K, g, rc, pb, thrb, pass_k(K, cvisc_b, K.massbound, p.vr.w), bc, poscell,
+                                           velrhop, press, sA, sB, sC, ft, ftp1);
+        } else {
+          bnd = pass_s<TDENSITY, 1, FT, S>(K, g, rc, p, thr, pass_k(K, cvisc_b, K.massbound, p.vr.w), bc, poscell,
+                                           velrhop, press, sA, sB, sC, ft, ftp1);
+        }
       }
       if (act && bitem) {
         // InteractionForcesBound store (JSphCpu.cpp:617-621) onto the reset ar = 0.
@@ -852,13 +876,49 @@ __global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const unsigned* __restrict__ bc, DivGrid g, KConst K, float4* __restrict__ arace, FtRec ft) {
   fluid_tiled<TDENSITY, FT, S>(sc, items, qctr, poscell, velrhop, press, bc, g, K, arace, ft);
 }
+// FTMODE_Ext (RigidAlgorithm 0 and 2): kernels of their own (TDENSITY | 32, FT records), so that
+// every instantiation above stays what it was.
+template <int TDENSITY, int S = 1>
+__global__ __launch_bounds__(TB) void k_fluid_tiled_ext(DevScalars* __restrict__ sc, const uint4* __restrict__ items,
+                                                        unsigned* __restrict__ qctr,
+                                                        const float4* __restrict__ poscell,
+                                                        const float4* __restrict__ velrhop,
+                                                        const float* __restrict__ press,
+                                                        const unsigned* __restrict__ bc, DivGrid g, KConst K,
+                                                        float4* __restrict__ arace, FtRec ft) {
+  fluid_tiled<TDENSITY | 32, true, S>(sc, items, qctr, poscell, velrhop, press, bc, g, K, arace, ft);
+}
+template <int TDENSITY, int S = 1>
+__global__ __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_fluid_tiled_ext_w4(
+    DevScalars* __restrict__ sc, const uint4* __restrict__ items, unsigned* __restrict__ qctr,
+    const float4* __restrict__ poscell, const float4* __restrict__ velrhop, const float* __restrict__ press,
+    const unsigned* __restrict__ bc, DivGrid g, KConst K, float4* __restrict__ arace, FtRec ft) {
+  fluid_tiled<TDENSITY | 32, true, S>(sc, items, qctr, poscell, velrhop, press, bc, g, K, arace, ft);
+}
 
+// The 4-wave register budget where the FTMODE_Ext body fits it without scratch: not the Cubic
+// DDT1 / DDT2 forms (17, 18, 26: 16-24 B of scratch per lane under the budget), which keep the
+// compiler's allocation.
+template <int TD>
+constexpr bool tiled_ext_w4() {
+  return TD == 1 || TD == 19 || TD == 27;
+}
 
 template <int S>
 static void launch_fluid_tiled_s(hipStream_t stm, unsigned nblocks, DevScalars* sc, const uint4* items,
                                  unsigned* qctr, const float4* poscell, const float4* velrhop, const float* press,
                                  const unsigned* begincell, DivGrid g, const KConst& K, float4* arace,
-                                 const FtRec& ft, unsigned reserve) {
+                                 const FtRec& ft, unsigned reserve, bool ftext) {
+#define SPH_TILED_EXT(TD)                                                                                      \
+  do {                                                                                                         \
+    if constexpr (tiled_ext_w4<TD>())                                                                           \
+      hipLaunchKernelGGL((k_fluid_tiled_ext_w4<TD, S>),                                                        \
+                         dim3(fit_grid((const void*)&k_fluid_tiled_ext_w4<TD, S>, nblocks, TB, reserve)), dim3(TB), 0, stm, \
+                         sc, items, qctr, poscell, velrhop, press, begincell, g, K, arace, ft);                \
+    else                                                                                                       \
+      hipLaunchKernelGGL((k_fluid_tiled_ext<TD, S>), dim3(fit_grid((const void*)&k_fluid_tiled_ext<TD, S>, nblocks, TB, reserve)), \
+                         dim3(TB), 0, stm, sc, items, qctr, poscell, velrhop, press, begincell, g, K, arace, ft); \
+  } while (0)
 #define SPH_TILED(TD, FTB)                                                                                     \
   do {                                                                                                         \
     if constexpr (tiled_w4<TD, FTB>())                                                                          \
@@ -872,7 +932,22 @@ static void launch_fluid_tiled_s(hipStream_t stm, unsigned nblocks, DevScalars* 
   // DDT 2/3 with the binomial series of the hydrostatic term (K.ddtseries) as TDENSITY | 8
   // and the Cubic spline kernel as TDENSITY | 16
   const int td = ((K.tdensity >= 2 && K.ddtseries) ? K.tdensity | 8 : K.tdensity) | (K.cubic ? 16 : 0);
-  if (ft.massp) {
+  if (ft.massp && ftext) {
+    switch (td) {
+      case 0: SPH_TILED_EXT(0); break;
+      case 1: SPH_TILED_EXT(1); break;
+      case 2: SPH_TILED_EXT(2); break;
+      case 3: SPH_TILED_EXT(3); break;
+      case 10: SPH_TILED_EXT(10); break;
+      case 11: SPH_TILED_EXT(11); break;
+      case 16: SPH_TILED_EXT(16); break;
+      case 17: SPH_TILED_EXT(17); break;
+      case 18: SPH_TILED_EXT(18); break;
+      case 19: SPH_TILED_EXT(19); break;
+      case 26: SPH_TILED_EXT(26); break;
+      default: SPH_TILED_EXT(27); break;
+    }
+  } else if (ft.massp) {
     switch (td) {
       case 0: SPH_TILED(0, true); break;
       case 1: SPH_TILED(1, true); break;
@@ -904,12 +979,13 @@ static void launch_fluid_tiled_s(hipStream_t stm, unsigned nblocks, DevScalars* 
     }
   }
 #undef SPH_TILED
+#undef SPH_TILED_EXT
 }
 
 void launch_fluid_tiled(hipStream_t stm, unsigned nblocks, DevScalars* sc, const uint4* items, unsigned* qctr,
                         const float4* poscell, const float4* velrhop, const float* press, const unsigned* begincell,
                         DivGrid g, const KConst& K, float4* arace, const typecode* code, const float* ftmassp,
-                        unsigned reserve) {
+                        unsigned reserve, bool ftext) {
   const FtRec ft = {code, ftmassp};
 #ifdef SPH_DIAG_HEADLINE_ONLY
   // diagnostic builds (kernel A/B at cfg2 only): the one instantiation of BASELINE cfg2
@@ -919,10 +995,11 @@ void launch_fluid_tiled(hipStream_t stm, unsigned nblocks, DevScalars* sc, const
                      dim3(TB), 0, stm, sc, items, qctr, poscell, velrhop, press, begincell, g, K, arace, ft);
 #else
   if (K.scelldiv == 2)
-    launch_fluid_tiled_s<2>(stm, nblocks, sc, items, qctr, poscell, velrhop, press, begincell, g, K, arace, ft, reserve);
+    launch_fluid_tiled_s<2>(stm, nblocks, sc, items, qctr, poscell, velrhop, press, begincell, g, K, arace, ft, reserve,
+                            ftext);
   else
     launch_fluid_tiled_s<1>(stm, nblocks, sc, items, qctr, poscell, velrhop, press, begincell, g, K, arace, ft,
-                            reserve);
+                            reserve, ftext);
 #endif
 }
 

@@ -338,7 +338,7 @@ void launch_divide_inc(hipStream_t stm, unsigned cap, DevScalars* sc, const Part
 // sorted particles) the kernel reads the p2 codes (JSphCpu.cpp:692-703).
 void launch_interaction(hipStream_t stm, unsigned cap, DevScalars* sc, const float4* poscell, const float4* velrhop,
                         const float* press, const unsigned* begincell, DivGrid g, const KConst& K, float4* arace,
-                        const typecode* code = nullptr, const float* ftmassp = nullptr);
+                        const typecode* code = nullptr, const float* ftmassp = nullptr, bool ftext = false);
 // Bound p1 only (grid over the bound capacity) — used beside the tiled fluid kernel.
 void launch_interaction_bound(hipStream_t stm, unsigned npbcap, DevScalars* sc, const float4* poscell,
                               const float4* velrhop, const unsigned* begincell, DivGrid g, const KConst& K,
@@ -366,7 +366,22 @@ constexpr size_t QCTR_BYTES = size_t(QCTR_COPIES) * QCTR_WORDS * sizeof(unsigned
 void launch_fluid_tiled(hipStream_t stm, unsigned nblocks, DevScalars* sc, const uint4* items, unsigned* qctr,
                         const float4* poscell, const float4* velrhop, const float* press, const unsigned* begincell,
                         DivGrid g, const KConst& K, float4* arace, const typecode* code = nullptr,
-                        const float* ftmassp = nullptr, unsigned reserve = 0);
+                        const float* ftmassp = nullptr, unsigned reserve = 0, bool ftext = false);
+// ftext (both kernels, with ftmassp): FTMODE_Ext (RigidAlgorithm 0 and 2) — the pairs bound p1 -
+// floating p2 and floating p1 - bound / floating p2 are left to the DEM pass or to nothing
+// (JSphCpu.cpp:594,705), in instantiations of their own.
+
+// ---- DEM collisions of floating bodies (sph_dem.hip; JSphCpu::InteractionForcesDEM) ----
+// StDemData of a block (JSph::LoadDemData), indexed by the particle code's type and value.
+struct DemRec {
+  float mass, tau, kfric, restitu, massp, pad0, pad1, pad2;
+};
+constexpr unsigned DEM_TABLE = unsigned(CODE_MASKTYPE | CODE_MASKVALUE) + 1u;
+// After the pair sums of Interaction_Forces: the contact accelerations of every floating particle
+// added to arace, their dt folded into the ViscDt slots, and |ace|^2 of [npb, np) reduced again
+// into the (cleared) AceMax slots.  interstep selects DemDtForce (DevScalars::demdtforce).
+void launch_dem(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, const DivGrid& g, float dp,
+                const DemRec* dem, const unsigned* begincell, const PartArrays& a, int interstep, float4* arace);
 // mDBC boundary correction (sph_mdbc.hip; JSphCpu.cpp:1020-1187): density of every
 // boundary particle p1 < npbok with a normal extrapolated from its ghost node; press
 // refreshed.  `normal` is indexed by idp; list[npbcap] + nlist: scratch of the

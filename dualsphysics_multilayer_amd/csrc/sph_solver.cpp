@@ -1565,24 +1565,31 @@ void SphGpuSingle::Interaction_Forces(int interstep) {
       // arrival.  The interior kernel leaves a few block slots free so that the transfer and
       // scatter kernels start at once.
       launch_fluid_tiled(stream, nblocks_tiled_, sc_, items_, qa, poscell_, cur_.velrhop, press_, begincell_, G, K,
-                         arace_, cur_.code, ftmassp_, 64);
+                         arace_, cur_.code, ftmassp_, 64, ftext_);
       GhostCollect(xstream_);
       launch_fluid_tiled(xstream_, nblocks_tiled_, sc_, items_, qf, poscell_, cur_.velrhop, press_, begincell_, G,
-                         K, arace_, cur_.code, ftmassp_);
+                         K, arace_, cur_.code, ftmassp_, 0, ftext_);
       check_hip(hipEventRecord(ev_ghost_, xstream_), "ghosts: event");
       check_hip(hipStreamWaitEvent(stream, ev_ghost_, 0), "ghosts: join");
       ghost_pending_ = false;
     } else {
       launch_fluid_tiled(stream, nblocks_tiled_, sc_, items_, qa, poscell_, cur_.velrhop, press_, begincell_, G, K,
-                         arace_, cur_.code, ftmassp_);
+                         arace_, cur_.code, ftmassp_, 0, ftext_);
       if (ghost_split_)  // the ghosts are in: the face items right after
         launch_fluid_tiled(stream, nblocks_tiled_, sc_, items_, qf, poscell_, cur_.velrhop, press_, begincell_,
-                           G, K, arace_, cur_.code, ftmassp_);
+                           G, K, arace_, cur_.code, ftmassp_, 0, ftext_);
     }
   } else {
     begin0();
     launch_interaction(stream, cap_, sc_, poscell_, cur_.velrhop, press_, begincell_, G, K, arace_, cur_.code,
-                       ftmassp_);
+                       ftmassp_, ftext_);
+  }
+  if (demtab_) {
+    // JSphCpu::InteractionForcesDEM (JSphCpu.cpp:975), added onto the pair sums; its dt goes
+    // into the ViscDt slots.  AceMax starts over: a contact can lower the |ace| that held the
+    // pair-sum maximum, and k_dem reduces the final |ace|^2 of [npb, np).
+    check_hip(hipMemsetAsync(&sc_->red[RED_ACEMAX2][0], 0, 4 * RED_SLOTS, stream), "reset acemax");
+    launch_dem(stream, cap_, sc_, K, G, float(C.dp), demtab_, begincell_, cur_, interstep, arace_);
   }
   if (acc_.n) {
     // JDsAccInput::RunCpu (JSphCpu.cpp:444), added onto the pair sums.  The interaction's
@@ -2375,6 +2382,51 @@ void SphGpuSingle::SetFloatings(unsigned nft, const SphFloatingDef* defs, double
   Sync();
 }
 
+// RigidAlgorithm (JSph.cpp:599-603): FTMODE_Ext's pair rule in the interaction kernels and, with
+// use_dem, the StDemData table of the DEM pass (JSph.cpp:1114-1130) and DemDtForce (JSph.cpp:
+// 2091-2098: DtIni, or the restart PART's value).
+void SphGpuSingle::SetRigid(int ftmode, bool use_dem, unsigned ndem, const SphDemDef* dem, double demdtforce) {
+  if (ftmode != SPH_FTMODE_SPH && ftmode != SPH_FTMODE_EXT) throw SphError(SPH_ERR_ARG, "Rigid algorithm is not valid.");
+  if (ftmode == SPH_FTMODE_SPH) {
+    if (use_dem) throw SphError(SPH_ERR_ARG, "DEM needs SPH_FTMODE_EXT (RigidAlgorithm=2)");
+    if (ftext_) throw SphError(SPH_ERR_STATE, "the rigid algorithm is configured once, before the first step");
+    return;
+  }
+  if (slab()) throw SphError(SPH_ERR_ARG, "RigidAlgorithm 0 and 2 (FTMODE_Ext, DEM) run on a single domain only");
+  if (stepped_ || ftext_) throw SphError(SPH_ERR_STATE, "the rigid algorithm is configured once, before the first step");
+  if (!ftbodies_) throw SphError(SPH_ERR_STATE, "configure the floating bodies before their rigid algorithm");
+  const char* bad = nn_ ? "NN multiphase" : normal_ ? "mDBC" : ext_ ? (sps_ ? "Laminar+SPS viscosity" : "Shifting") : nullptr;
+  if (bad) throw SphError(SPH_ERR_UNSUPPORTED, std::string(bad) + " with RigidAlgorithm 0 or 2 is not implemented");
+  if (use_dem) {
+    if (!ndem || !dem) throw SphError(SPH_ERR_ARG, "DEM needs the data of every boundary block");
+    std::vector<DemRec> tab(DEM_TABLE);
+    std::memset(tab.data(), 0, sizeof(DemRec) * tab.size());
+    std::vector<char> have(DEM_TABLE, 0);
+    for (unsigned i = 0; i < ndem; i++) {
+      const SphDemDef& d = dem[i];
+      if (d.code >= DEM_TABLE || d.code >= unsigned(CODE_TYPE_FLUID)) throw SphError(SPH_ERR_ARG, "DEM data: not a boundary block's code");
+      if (have[d.code]) throw SphError(SPH_ERR_ARG, "DEM data: a block is given twice");
+      have[d.code] = 1;
+      DemRec& r = tab[d.code];
+      r.mass = d.mass;
+      r.tau = d.tau;
+      r.kfric = d.kfric;
+      r.restitu = d.restitu;
+      r.massp = d.massp;
+    }
+    for (int c = 0; c < nftbodies_; c++)
+      if (!have[unsigned(CODE_TYPE_FLOATING) + unsigned(c)]) throw SphError(SPH_ERR_ARG, "DEM data: a floating body has none");
+    check_hip(hipSetDevice(device), "hipSetDevice");
+    check_hip(hipMalloc((void**)&demtab_, sizeof(DemRec) * tab.size()), "hipMalloc DEM data");
+    allocs_.push_back(demtab_);
+    check_hip(hipMemcpy(demtab_, tab.data(), sizeof(DemRec) * tab.size(), hipMemcpyHostToDevice), "upload DEM data");
+    const double d0 = demdtforce > 0 ? demdtforce : C.dtini;
+    Sync();
+    check_hip(hipMemcpy(&sc_->demdtforce, &d0, sizeof(double), hipMemcpyHostToDevice), "set DemDtForce");
+  }
+  ftext_ = true;
+}
+
 // FtLinearVel / FtAngularVel / FtLinearForce / FtAngularForce of one body (JSph.cpp:1060-1082):
 // the rows are re-uploaded as one buffer with a {first row, rows} descriptor per table.
 void SphGpuSingle::SetFloatingTable(unsigned body, int kind, unsigned n, const double* times, const double* values) {
@@ -2537,6 +2589,7 @@ SphRunStats SphGpuSingle::Stats() {
   r.viscdtmax = s.last_viscdt;
   r.viscetadtmax = s.last_visceta;
   r.fused_updates = fused_updates_;
+  r.dem_dtforce = demtab_ ? s.demdtforce : 0.0;
   return r;
 }
 

@@ -52,7 +52,8 @@ void partfloat_write(const std::string& path, const char* app, uint32_t mkboundf
                      const uint16_t* mkbound, const uint32_t* begin, const uint32_t* count, const float* mass,
                      const float* massp, const float* radius, uint32_t nparts, const uint32_t* cpart,
                      const uint32_t* step, const double* timestep, const double* center, const float* fvel,
-                     const float* fomega, const float* facelin, const float* faceang);
+                     const float* fomega, const float* facelin, const float* faceang,
+                     const double* demdtforce = nullptr);
 uint32_t normals_read(const std::string& path, uint32_t cap, double* out);
 void partfloat_read(const std::string& path, uint32_t cpart, uint32_t nft, double* center, float* fvel,
                     float* fomega, double* timestep);
@@ -119,6 +120,8 @@ class SphGpuSingle {
   void SetMotionTree(unsigned nnode, const SphMotionObj* nodes, unsigned nmov, const SphMotionMov* movs, unsigned nevt,
                      const SphMotionEvent* evts, unsigned nrows, const double* rows);
   void SetFloatings(unsigned nft, const SphFloatingDef* defs, double ftpause);
+  // RigidAlgorithm of the floating bodies: FTMODE_Ext pair rule and the DEM pass (sph_dem.hip)
+  void SetRigid(int ftmode, bool use_dem, unsigned ndem, const SphDemDef* dem, double demdtforce);
   // Imposed velocity / external force table of one body (SPH_FTTAB_*), before the first step.
   void SetFloatingTable(unsigned body, int kind, unsigned n, const double* times, const double* values);
   // DtFixedFile / ViscoTime tables (SPH_TTAB_*); n = 0 removes one.
@@ -283,6 +286,8 @@ class SphGpuSingle {
   void UploadFloatingTables();    // (again at a restart: the lookups start over, as new JLinearValues)
   std::vector<std::vector<double4>> fttabs_;  // host copy, [body * 4 + kind]
   int nftbodies_ = 0;
+  bool ftext_ = false;           // FTMODE_Ext: the interaction kernels' instantiations of their own
+  DemRec* demtab_ = nullptr;     // DEM on: StDemData by particle code (DEM_TABLE entries)
   void* dttab_ = nullptr;        // DtFixedFile rows: times [n], dt in ms [n] (double)
   void* viscotab_ = nullptr;     // ViscoTime rows: times [n], Visco [n] (float)
   unsigned nftp_ = 0;            // floating particles of the case (CaseNfloat)

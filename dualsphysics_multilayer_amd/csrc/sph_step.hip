@@ -107,6 +107,7 @@ __global__ void k_dt(DevScalars* __restrict__ sc, KConst K, double cfl, double d
     if (dttrace && tracecap) dttrace[sc->nstep % tracecap] = stepdt;
     sc->time += stepdt;
     sc->last_dt = stepdt;
+    sc->demdtforce = stepdt;  // DemDtForce = dt (JSphCpuSingle.cpp:678,709)
     sc->nstep++;
   }
   // ViscoTime: Visco of the next step, at its TimeStep (JSphCpuSingle.cpp:1092), once the

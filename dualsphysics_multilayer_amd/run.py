@@ -173,6 +173,7 @@ class CaseRun:
         return dict(app_name=self.app_name, case_name=c.case_name, cpart=cpart, nout=nout, step=step,
                     timestep=float(st["time"]),
                     symplectic_dtpre=float(st["sym_dtpre"]) if c.step_algorithm == 2 else 0.0,
+                    dem_dtforce=float(st.get("dem_dtforce", 0.0)),  # UseDEM (JSph.cpp:2597)
                     np_total=c.case_np, case_np=c.case_np, case_nfixed=c.case_nfixed, case_nfluid=c.case_nfluid,
                     case_nmoving=getattr(c, "case_nmoving", 0), case_nfloat=getattr(c, "case_nfloat", 0),
                     dp=c.dp, h=c.h, b=c.cteb, rhop0=c.rhop0, gamma=c.gamma, massbound=c.massbound,
@@ -230,7 +231,8 @@ class CaseRun:
                 from .core import write_partfloat
 
                 self._ftparts.append(dict(cpart=cpart, step=step, time=float(st["time"]),
-                                          bodies=self.solver.floatings()))
+                                          bodies=self.solver.floatings(),
+                                          demdtforce=float(st.get("dem_dtforce", 0.0))))
                 # rewritten whole into a temporary file and renamed over the previous one, so a
                 # crash mid-write never truncates the records of earlier PARTs
                 path = os.path.join(self.dirout, "PartFloat.fbi4")

@@ -2,7 +2,8 @@
 (SURVEY.md §8(f) row 2).
 
 Mirrors what ``JSph`` reads before the first step, restricted to what the hot path of
-this core runs (fixed and moving DBC/mDBC boundaries, RigidAlgorithm=1 floating bodies, fluid,
+this core runs (fixed and moving DBC/mDBC boundaries, floating bodies with RigidAlgorithm 0, 1 or 2
+and the materials of ``<properties>``, fluid,
 Wendland, artificial viscosity, DDT 0-3,
 Verlet / Symplectic, periodic boundaries); anything else raises ``CaseError`` the way the
 reference refuses an invalid configuration, never silently ignored:
@@ -319,6 +320,170 @@ def _config_domain(p: _Params) -> _DomainCfg:
     return d
 
 
+# ---- <particles><properties> (JCaseProperties) ---------------------------------------------
+def _atof(v: str) -> float:
+    import re
+
+    m = re.match(r"\s*[-+]?(\d+\.?\d*|\.\d+)([eE][-+]?\d+)?", v)
+    return float(m.group(0)) if m else 0.0
+
+
+def _mk_range(text: str) -> set:
+    """JRangeFilter: "3,5-7" -> {3, 5, 6, 7}."""
+    out = set()
+    for part in text.split(","):
+        if not part:
+            continue
+        a, _, b = part.partition("-")
+        try:
+            lo = int(a)
+            hi = int(b) if b else lo
+        except ValueError:
+            raise CaseError(f"<properties><links>: the mk list {text!r} is not valid.") from None
+        out.update(range(lo, hi + 1))
+    return out
+
+
+def _props_sort(props: str) -> str:
+    """JCasePropLinks::GetPropsSort (JCaseProperties.cpp:387-411): the names of an "a+b"
+    composition without repeats, in alphabetical order."""
+    return "+".join(sorted({p for p in props.split("+") if p}))
+
+
+class CaseProperties:
+    """``<particles><properties>`` as the solver reads it (JCaseProperties::ReadXml,
+    JCaseProperties.cpp:699-715): ``<property name= attr=...>`` with its inline values (attributes)
+    and sub-values (``<Name attr=.../>`` children), ``<propertyfile file= path=>`` (the
+    ``<property>`` children of the node ``path`` of another XML file) and
+    ``<links><link mk= property="a+b">``.  Names that begin with '_' are remarks."""
+
+    def __init__(self, node=None, casedir: str = "."):
+        self.props = {}  # name -> {"values": {name: str}, "subs": {name: {subname: str}}, "order": [names]}
+        self.links = []  # (type, set of mk, props)
+        if node is None:
+            return
+        links = node.find("links")
+        if links is not None:
+            for ele in links.findall("link"):
+                kind = "mkbound" if ele.get("mkbound") is not None else "mkfluid" if ele.get("mkfluid") is not None else "mk"
+                for att in (kind, "property"):
+                    if ele.get(att) is None:
+                        raise CaseError(f"The attribute '{att}' of 'link' is missing.")
+                mks, props = ele.get(kind).replace(" ", ""), ele.get("property").replace(" ", "")
+                if mks and props:
+                    self.links.append((kind, _mk_range(mks), props))
+        for ele in node:
+            cmd = ele.tag
+            if not isinstance(cmd, str) or cmd.startswith("_"):
+                continue
+            if cmd == "property":
+                self._read_property(ele)
+            elif cmd == "propertyfile":
+                self._read_file(ele, casedir)
+            elif cmd != "links":
+                raise CaseError(f"<properties>: the element <{cmd}> is not valid.")
+        for _, _, props in self.links:  # CheckLinks
+            for pro in props.split("+"):
+                if pro and pro not in self.props:
+                    raise CaseError(f"Property '{pro}' not found.")
+
+    def _read_property(self, ele) -> None:
+        name = ele.get("name")
+        if name is None:
+            raise CaseError("The attribute 'name' of 'property' is missing.")
+        pro = self.props.setdefault(name, dict(values={}, subs={}, order=[]))  # AddProperty: an existing one goes on
+
+        def add(vname):
+            if vname.lower() == "name":
+                raise CaseError("The name of value cannot be 'name'.")
+            if vname in pro["order"]:
+                raise CaseError("Value already exists.")
+            pro["order"].append(vname)
+
+        for k, v in ele.attrib.items():
+            if k != "name" and not k.startswith("_"):
+                add(k)
+                pro["values"][k] = v
+        for sub in ele:
+            if not isinstance(sub.tag, str) or sub.tag.startswith("_"):
+                continue
+            for k, v in sub.attrib.items():
+                if k.startswith("_"):
+                    continue
+                if sub.tag in pro["values"]:
+                    raise CaseError("Value already exists.")
+                if sub.tag not in pro["subs"]:
+                    add(sub.tag)
+                    pro["subs"][sub.tag] = {}
+                if k in pro["subs"][sub.tag]:
+                    raise CaseError("Name-Value already exists.")
+                pro["subs"][sub.tag][k] = v
+
+    def _read_file(self, ele, casedir: str) -> None:
+        for att in ("file", "path"):
+            if ele.get(att) is None:
+                raise CaseError(f"The attribute '{att}' of 'propertyfile' is missing.")
+        file, path = ele.get("file"), ele.get("path")
+        fn = file if os.path.isabs(file) else os.path.join(casedir, file)
+        if not os.path.isfile(fn):
+            raise CaseError(f"File of properties was not found: {file}")
+        root = ET.parse(fn).getroot()
+        parts = path.split(".")
+        node = root if parts[0] == root.tag else None
+        for part in parts[1:]:
+            node = node.find(part) if node is not None else None
+        if node is None:
+            raise CaseError(f"Cannot find the element '{path}'. File: {file}")
+        for sub in node:
+            if sub.tag == "property":
+                self._read_property(sub)
+
+    def property_mk(self, mk: int) -> str:
+        """JCaseProperties::GetPropertyMk -> JCasePropLinks::GetProps(mk) (JCaseProperties.cpp:
+        486-498): the solver's XML holds links by mk only (GenCase rewrites the others)."""
+        props = ""
+        for kind, mks, pro in self.links:
+            if kind != "mk":
+                raise CaseError("Type of links (mkbound or mkfluid) is invalid.")
+            if mk in mks:
+                props += pro + "+"
+        return _props_sort(props)
+
+    def _value(self, props: str, name: str):
+        """GetValuePtr(props, name): the value of the first property of the composition that has it."""
+        for pro in props.split("+"):
+            if not pro:
+                continue
+            if pro not in self.props:
+                raise CaseError(f"Property '{pro}' not found.")
+            p = self.props[pro]
+            if name in p["values"]:
+                return p["values"][name]
+            if name in p["subs"]:
+                return p["subs"][name]
+        return None
+
+    def exists_value(self, props: str, name: str) -> bool:
+        return self._value(props, name) is not None
+
+    def value_float(self, props: str, name: str) -> float:
+        v = self._value(props, name)
+        if v is None:
+            raise CaseError(f"Value '{name}' not found.")
+        if isinstance(v, dict):
+            raise CaseError("Value has one or more several subvalues.")
+        return float(np.float32(_atof(v)))
+
+    def exists_subvalue(self, props: str, name: str, sub: str) -> bool:
+        v = self._value(props, name)
+        return isinstance(v, dict) and sub in v
+
+    def subvalue_float(self, props: str, name: str, sub: str, default: float) -> float:
+        if not self.exists_subvalue(props, name, sub):
+            return default
+        return float(np.float32(_atof(self._value(props, name)[sub])))
+
+
 # ---- the case -----------------------------------------------------------------------------
 # command-line overrides (JSphCfgRun -> JSph::LoadConfigCommands) this core takes
 OVERRIDES = ("step_algorithm", "verlet_steps", "tdensity", "ddtvalue", "visco", "viscoboundfactor", "cellmode",
@@ -457,8 +622,7 @@ class XmlCase:
             self._check_periodic_walls()
         if self.floatings and self.partbegin:
             self._restart_floatings()
-        if self.floatings and self.rigidalgorithm != 1:
-            raise CaseError("Only RigidAlgorithm=1 (SPH) floating bodies are supported by this core.")
+        self._config_rigid(h)
         # case limits (JPartsLoad4 CasePosMin/Max; computed when the file has none)
         cmin, cmax = list(h["case_posmin"]), list(h["case_posmax"])
         if cmin == cmax:
@@ -499,6 +663,64 @@ class XmlCase:
             f["center"] = tuple(float(x) for x in st["center"][k])
             f["linvelini"] = tuple(float(x) for x in st["fvel"][k])
             f["angvelini"] = tuple(float(x) for x in st["fomega"][k])
+
+    # -- RigidAlgorithm (JSph.cpp:599-603, 1099-1140) -------------------------------------------
+    def _config_rigid(self, h) -> None:
+        """0 collision-free (FTMODE_Ext), 1 SPH (FTMODE_Sph), 2 SPH-DCDEM (FTMODE_Ext + UseDEM); 3
+        (Chrono) needs the closed library.  Sets ``ftmode`` (SPH_FTMODE_*), ``use_dem``, ``demdata``
+        (one entry per boundary block) and ``demdtforce0`` (a restart's DemDtForce, else 0)."""
+        rig = self.rigidalgorithm
+        if rig == 3:
+            raise CaseError("RigidAlgorithm=3 (Project Chrono coupling) is not supported by this core.")
+        self.use_dem, self.demdata, self.demdtforce0 = False, [], 0.0
+        self.messages = getattr(self, "messages", [])
+        self.ftmode = 0 if not self.floatings else (1 if rig == 1 else 2)
+        if not self.floatings:
+            if rig == 2:  # JSph.cpp:1100-1103
+                self.messages.append("The use of DEM was disabled because there are no floating objects...")
+            return
+        if rig == 1:
+            return
+        # what this core runs with FTMODE_Ext: DBC, artificial viscosity, no shifting
+        bad = [what for on, what in ((self.tboundary == 2, "mDBC"), (self.tvisco != 1, "Laminar+SPS viscosity"),
+                                     (self.shift_mode != 0, "Shifting")) if on]
+        if bad:
+            raise CaseError(f"{', '.join(bad)} with RigidAlgorithm={rig}: not supported by this core.")
+        if rig == 2:
+            self.use_dem = True
+            self.demdata = self._load_demdata()
+            if self.partbegin:  # JSph.cpp:2098
+                self.demdtforce0 = float(h.get("dem_dtforce", 0.0))
+
+    # -- JSph::LoadDemData (JSph.cpp:1189-1227) for every boundary block (JSph.cpp:1120-1130) ----
+    def _load_demdata(self) -> list:
+        f32 = np.float32
+        fltmax = float(np.finfo(np.float32).max)
+        out = []
+        for b in self.blocks:
+            if b["type"] == "fluid":
+                continue
+            pr, props = self.properties, b["property"]
+            desc = f"Object mk={b['mk']} (mkbound={b['mktype']})"
+            for name in ("Kfric", "Restitution_Coefficient", "Young_Modulus", "PoissonRatio"):
+                if not pr.exists_subvalue(props, name, "value"):
+                    raise CaseError(f"{desc} - Value of {name} is invalid. "
+                                    "(RigidAlgorithm=2 reads it from the block's <properties>)")
+            kfric = pr.subvalue_float(props, "Kfric", "value", fltmax)
+            restitu = pr.subvalue_float(props, "Restitution_Coefficient", "value", fltmax)
+            young = pr.subvalue_float(props, "Young_Modulus", "value", fltmax)
+            poisson = pr.subvalue_float(props, "PoissonRatio", "value", fltmax)
+            if pr.exists_value(props, "Kfric_User"):
+                kfric = pr.value_float(props, "Kfric_User")
+            if pr.exists_value(props, "Restitution_Coefficient_User"):
+                restitu = pr.value_float(props, "Restitution_Coefficient_User")
+            mass, massp = 0.0, float(f32(self.massbound))
+            if b["type"] == "floating":
+                mass, massp = float(f32(b["floating"]["massbody"])), float(f32(b["floating"]["masspart"]))
+            tau = float((f32(1) - f32(poisson) * f32(poisson)) / f32(young)) if young else 0.0
+            out.append(dict(code=int(b["code"]), mk=b["mk"], mass=mass, massp=massp, tau=tau, kfric=kfric,
+                            restitu=restitu, young=young, poisson=poisson))
+        return out
 
     # -- JSph::LoadBoundNormals (JSph.cpp:1265-1295) ------------------------------------------
     def _load_normals(self) -> np.ndarray:
@@ -672,7 +894,8 @@ class XmlCase:
                     continue
                 raise CaseError(f"<particles>: unknown block <{e.tag}>.")
             b = dict(type=e.tag, mk=int(e.get("mk")), begin=int(e.get("begin")), count=int(e.get("count")),
-                     mktype=int(e.get("mkfluid") if e.tag == "fluid" else e.get("mkbound")))
+                     mktype=int(e.get("mkfluid") if e.tag == "fluid" else e.get("mkbound")),
+                     property=e.get("property", ""))
             if e.tag == "floating":
                 b["floating"] = self._load_floating(e, self._dircase)
             blocks.append(b)
@@ -691,6 +914,12 @@ class XmlCase:
         for k in kinds:
             for i, b in enumerate(bytype[k]):
                 b["code"] = base[k] | i
+        # <properties> and the blocks' property attribute against its links (JCaseParts::ReadXml,
+        # JCaseParts.cpp:492-518)
+        self.properties = CaseProperties(node.find("properties"), self._dircase)
+        for b in blocks:
+            if b["property"] != self.properties.property_mk(b["mk"]):
+                raise CaseError(f"Property information of mk={b['mk']} does not correspond to Links configuration.")
         self.blocks = blocks
         self.case_np = begin
         self.case_nfixed = sum(b["count"] for b in bytype["fixed"])

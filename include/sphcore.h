@@ -59,6 +59,8 @@
  *   sph_solver_set_accinputs ... JDsAccInput::RunCpu in PreInteractionVars_Forces (JSphCpu.cpp:444)
  *   sph_solver_set_damping ..... JSphCpu::RunDamping at the end of ComputeStep_Ver / _Sym
  *                                (JSphCpuSingle.cpp:683,717; JDsDamping.cpp)
+ *   sph_solver_set_rigid ....... RigidAlgorithm 0 / 2: FTMODE_Ext in Interaction_Forces and
+ *                                JSphCpu::InteractionForcesDEM after it (JSphCpu.cpp:828-925,975)
  *   SphCaseDef.peri_active ..... periodic boundaries: JSphCpuSingle::RunPeriodic before every
  *                                divide (JSphCpuSingle.cpp:361-431), the wrap of JSphCpu::UpdatePos
  *                                (JSphCpu.cpp:1254-1291); single domain, DBC, no bodies
@@ -73,7 +75,7 @@
 extern "C" {
 #endif
 
-#define SPH_ABI_VERSION 16
+#define SPH_ABI_VERSION 17
 
 typedef enum {
   SPH_OK = 0,
@@ -273,6 +275,7 @@ typedef struct SphRunStats {
                              motion or SPH_DIVIDE=full: the divide classifies)  */
   uint32_t npbper, npfper;/* periodic duplicates (boundary, fluid) after the last divide;
                              np, npb, npbok and every download count normal particles only */
+  double dem_dtforce;     /* DemDtForce after the last step (RigidAlgorithm=2; else 0) */
 } SphRunStats;
 
 /* Host particle view (SaveData layout: JSph::SaveData, JSph.cpp:2717). */
@@ -468,6 +471,7 @@ typedef struct SphPartHeader {
   float visco, viscoboundfactor;      /* ViscoValue, ViscoBoundFactor                     */
   float gravity[3];                   /* Gravity                                          */
   uint32_t mkbound, mkfluid;          /* Mk of the fixed and the fluid block              */
+  double dem_dtforce;                 /* DemDtForce (written if > 0: a DEM run; read on restart) */
 } SphPartHeader;
 
 /* Read a PART or case file.  With out == NULL (or out->n < Npok) only *hdr is filled;
@@ -556,7 +560,7 @@ int sph_solver_set_motion_tree(SphSolver* s, uint32_t nnode, const SphMotionObj*
                                const double* rows);
 
 /* Floating body (JCasePartBlock_Floating, JCaseParts.cpp:248-290 -> StFloatingData,
- * JSph.cpp:1046-1100), RigidAlgorithm=1 (SPH forces). */
+ * JSph.cpp:1046-1100); RigidAlgorithm=1 (SPH forces) unless sph_solver_set_rigid says otherwise. */
 typedef struct SphFloatingDef {
   uint32_t idbegin, count;     /* idp range of its particles                        */
   double massbody, masspart;   /* <massbody>, <masspart> (narrowed to float)        */
@@ -587,6 +591,34 @@ enum { SPH_FTTAB_LINVEL = 0, SPH_FTTAB_ANGVEL = 1, SPH_FTTAB_LINFORCE = 2, SPH_F
 int sph_solver_set_floating_table(SphSolver* s, uint32_t body, int32_t kind, uint32_t n, const double* times,
                                   const double* values);
 int sph_solver_floatings(SphSolver* s, uint32_t cap, SphFloatingState* out, uint32_t* nft);
+/* RigidAlgorithm of the floating bodies (JSph.cpp:599-603; TpFtMode, DualSphDef.h:433-441):
+ *   SPH_FTMODE_SPH  (RigidAlgorithm=1, the default): bodies meet walls and each other through
+ *                   the SPH pair forces;
+ *   SPH_FTMODE_EXT  (RigidAlgorithm=0 and 2): the SPH passes skip the pairs bound p1 - floating
+ *                   p2 and floating p1 - bound or floating p2 (the `compute` flag of
+ *                   JSphCpu.cpp:594,705); with use_dem (RigidAlgorithm=2) the DEM pass
+ *                   JSphCpu::InteractionForcesDEM (JSphCpu.cpp:828-925; SPH-DCDEM, Canelas et al.)
+ *                   follows the pair sums inside Interaction_Forces: Hertz stiffness, Cummins
+ *                   damping and Coulomb / elastic friction between every floating particle and the
+ *                   boundary and floating particles of other blocks closer than Dp, its time step
+ *                   folded into ViscDtMax, AceMax taken over the final accelerations.
+ * dem[ndem]: the StDemData of every boundary block (fixed, moving and floating) by its particle
+ * code (type | block index), as JSph::LoadDemData derives them (tau = (1 - poisson^2) / young;
+ * mass = the body's for a floating block, else 0; massp = the body's particle mass, else
+ * MassBound).  demdtforce: DemDtForce of a restart's PART (0: DtIni, JSph.cpp:2091-2098); then
+ * the device keeps it: the last step's dt under Verlet, dt/2 and dt before the Symplectic
+ * predictor's and corrector's interactions (JSphCpuSingle.cpp:678,700,709).
+ * Once, after sph_solver_set_floatings and before the first step; single domain, single phase,
+ * DBC, artificial viscosity, no shifting.  A slab solver takes SPH_FTMODE_SPH only and answers
+ * SPH_ERR_ARG to the others. */
+enum { SPH_FTMODE_NONE = 0, SPH_FTMODE_SPH = 1, SPH_FTMODE_EXT = 2 };
+typedef struct SphDemDef {
+  uint32_t code;                /* type | block index of the block's particles      */
+  float mass, massp;            /* StDemData::mass, massp                          */
+  float tau, kfric, restitu;    /* StDemData::tau, kfric, restitu                  */
+} SphDemDef;
+int sph_solver_set_rigid(SphSolver* s, int32_t ftmode, int32_t use_dem, uint32_t ndem, const SphDemDef* dem,
+                         double demdtforce);
 /* Time tables of the step (call before the first step, or after sph_solver_set_time; on
  * slabs on every rank; n >= 2 rows in any order, walked forward from the row of the last
  * lookup as the reference walks them (Position), n = 0 removes the table):
@@ -601,12 +633,13 @@ int sph_solver_set_time_table(SphSolver* s, int32_t kind, uint32_t n, const doub
 /* PartFloat.fbi4 (JPartFloatBi4Save::SaveInitial + AddPartFloat/SavePartFloat,
  * JPartFloatBi4.cpp:243-346): per-body head arrays [nft] and, per saved PART k, its
  * Cpart/Step/TimeStep and the body states center[k][nft][3], fvel, fomega, facelin,
- * faceang [k][nft][3]; readable by the reference's JPartFloatBi4Load (FloatingInfo). */
+ * faceang [k][nft][3]; readable by the reference's JPartFloatBi4Load (FloatingInfo).
+ * demdtforce[k]: DemDtForce of PART k (a DEM run, JSph.cpp:2705), NULL: 0. */
 int sph_partfloat_write(const char* path, const char* app, uint32_t mkboundfirst, uint32_t nft,
                         const uint16_t* mkbound, const uint32_t* begin, const uint32_t* count, const float* mass,
                         const float* massp, const float* radius, uint32_t nparts, const uint32_t* cpart,
                         const uint32_t* step, const double* timestep, const double* center, const float* fvel,
-                        const float* fomega, const float* facelin, const float* faceang);
+                        const float* fomega, const float* facelin, const float* faceang, const double* demdtforce);
 /* Restart of floating bodies (JSphCpu::InitFloating, JSphCpu.cpp:1885-1905): the state of
  * PART cpart in PartFloat.fbi4 (JPartFloatBi4Load::LoadPart) — center[nft][3], fvel, fomega
  * (any pointer may be NULL) and its TimeStep.  The reference restarts a body with these and
