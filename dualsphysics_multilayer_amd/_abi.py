@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-SPH_ABI_VERSION = 17
+SPH_ABI_VERSION = 18
 
 SPH_STATUS = {
     0: "SPH_OK",
@@ -267,6 +267,13 @@ class SphInterOut(C.Structure):
         ("viscdtmax", C.c_float),
         ("velmax", C.c_float),
         ("acemax", C.c_float),
+    ]
+
+
+class SphExtOut(C.Structure):
+    _fields_ = [
+        ("shiftposfs", C.POINTER(C.c_float)),
+        ("tau", C.POINTER(C.c_float)),
     ]
 
 

@@ -26,6 +26,7 @@ from ._abi import (
     HostParticles,
     SphCaseDef,
     SphConstants,
+    SphExtOut,
     SphInterOut,
     SphRunStats,
     SphPartHeader,
@@ -76,6 +77,7 @@ EXPORTED_SYMBOLS = (
     "sph_solver_dt_trace",
     "sph_download_particles",
     "sph_download_interaction",
+    "sph_download_ext",
     "sph_count_pairs",
     "sph_solver_set_time",
     "sph_solver_set_timing",
@@ -160,6 +162,7 @@ def load_library(path: str = LIB_PATH):
     L.sph_solver_dt_trace.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
     L.sph_download_particles.argtypes = [vp, vp]
     L.sph_download_interaction.argtypes = [vp, C.POINTER(SphInterOut)]
+    L.sph_download_ext.argtypes = [vp, C.POINTER(SphExtOut), C.c_int]
     L.sph_count_pairs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.sph_solver_set_timing.argtypes = [vp, C.c_int]
     L.sph_solver_set_timing_phases.argtypes = [vp, C.c_uint]
@@ -419,6 +422,22 @@ class SphGpuSingle:
         out = SphInterOut(ar.ctypes.data_as(C.POINTER(C.c_float)), ace.ctypes.data_as(C.POINTER(C.c_float)), 0, 0, 0)
         _check(load_library().sph_download_interaction(self._h, C.byref(out)))
         return dict(ar=ar, ace=ace, viscdtmax=out.viscdtmax, velmax=out.velmax, acemax=out.acemax)
+
+    def download_ext(self, keep_tau: bool = False) -> dict:
+        """One Interaction_Forces(1) on the current state and what only k_fluid_ext computes, in
+        device order: shiftposfs [np][4] (shifting; x = FLT_MAX where frozen) and tau [np][6]
+        (Laminar+SPS: xx, xy, xz, yy, yz, zz of the tensor this interaction computed); None for
+        an option the case does not have.  keep_tau: that tensor becomes the state's, as after a
+        step's interaction; else the state's stays.  Buffers start as NaN."""
+        n = self.stats()["np"]
+        cd = self.case.case_def()
+        fp = C.POINTER(C.c_float)
+        shift = np.full((n, 4), np.nan, np.float32) if cd["shift_mode"] else None
+        tau = np.full((n, 6), np.nan, np.float32) if cd["tvisco"] == 2 and cd["rheology"] == 1 else None
+        out = SphExtOut(shift.ctypes.data_as(fp) if shift is not None else fp(),
+                        tau.ctypes.data_as(fp) if tau is not None else fp())
+        _check(load_library().sph_download_ext(self._h, C.byref(out), int(bool(keep_tau))))
+        return dict(shiftposfs=shift, tau=tau)
 
     def count_pairs(self) -> np.ndarray:
         out = np.zeros(6, np.uint64)

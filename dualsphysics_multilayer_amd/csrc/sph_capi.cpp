@@ -136,6 +136,14 @@ int sph_download_interaction(SphSolver* s, SphInterOut* out) {
   NOT_MEMBER(s);
   return guard([&] { s->impl->DownloadInteraction(*out); });
 }
+int sph_download_ext(SphSolver* s, SphExtOut* out, int keep_tau) {
+  NEED(s && out);
+  if (s->member) {
+    g_last_error = "slab group member: the ext download is single-domain only";
+    return SPH_ERR_UNSUPPORTED;
+  }
+  return guard([&] { s->impl->DownloadExt(*out, keep_tau != 0); });
+}
 int sph_count_pairs(SphSolver* s, uint64_t out[6]) {
   NEED(s && out);
   return guard([&] { s->impl->CountPairs(out); });

@@ -2707,6 +2707,50 @@ void SphGpuSingle::DownloadInteraction(SphInterOut& out) {
   Sync();
 }
 
+// The outputs of k_fluid_ext that DownloadInteraction does not show: the shifting sums and the
+// SPS stress tensor of one Interaction_Forces(1) on the current state.
+void SphGpuSingle::DownloadExt(SphExtOut& out, bool keep_tau) {
+  if (slab()) throw SphError(SPH_ERR_UNSUPPORTED, "ext download is single-domain only");
+  if (out.tau && !sps_) throw SphError(SPH_ERR_STATE, "the case has no Laminar+SPS viscosity (no SPS stress tensor)");
+  if (out.shiftposfs && !shift_) throw SphError(SPH_ERR_STATE, "the case has no shifting (no shifting sums)");
+  if (!ext_) throw SphError(SPH_ERR_STATE, "the case has neither Laminar+SPS viscosity nor shifting");
+  Interaction_Forces(1);  // the new tensor is cur_.tau now, the one the pairs read taunew_
+  Stats();  // waits for the interaction; the counts are in sc_host_
+  const unsigned n = sc_host_->np, npb = sc_host_->npb;
+  if (out.shiftposfs) {
+    std::vector<float4> sp(n);
+    check_hip(hipMemcpy(sp.data(), shiftpos_, 16 * size_t(n), hipMemcpyDeviceToHost), "download shiftposfs");
+    for (unsigned p = 0; p < n; p++) {
+      const float4 v = p < npb ? make_float4(0.f, 0.f, 0.f, 0.f) : sp[p];
+      out.shiftposfs[4 * p] = v.x;
+      out.shiftposfs[4 * p + 1] = v.y;
+      out.shiftposfs[4 * p + 2] = v.z;
+      out.shiftposfs[4 * p + 3] = v.w;
+    }
+  }
+  if (out.tau) {
+    std::vector<float4> t(2 * size_t(n));
+    check_hip(hipMemcpy(t.data(), cur_.tau, 32 * size_t(n), hipMemcpyDeviceToHost), "download tau");
+    for (unsigned p = 0; p < n; p++) {
+      const float4 a = t[2 * size_t(p)], b = t[2 * size_t(p) + 1];
+      const bool bound = p < npb;
+      float* o = out.tau + 6 * size_t(p);
+      o[0] = bound ? 0.f : a.x;
+      o[1] = bound ? 0.f : a.y;
+      o[2] = bound ? 0.f : a.z;
+      o[3] = bound ? 0.f : a.w;
+      o[4] = bound ? 0.f : b.x;
+      o[5] = bound ? 0.f : b.y;
+    }
+  }
+  // an inspection leaves the state's tensor the one the next step starts from
+  if (sps_ && !keep_tau) std::swap(cur_.tau, taunew_);
+  // the device maxima as a fresh interaction would find them (DownloadInteraction)
+  check_hip(hipMemsetAsync(&sc_->red[RED_ACEMAX2][0], 0, 4 * RED_SLOTS, stream), "reset acemax");
+  check_hip(hipMemsetAsync(&sc_->red[RED_VISCDT][0], 0, 4 * RED_SLOTS, stream), "reset viscdt");
+  Sync();
+}
+
 unsigned SphGpuSingle::DownloadNormals(float* out, unsigned cap, int* usenormalsft) {
   if (!normal_) throw SphError(SPH_ERR_STATE, "the case has no mDBC normals");
   if (usenormalsft) *usenormalsft = ftnormals_ ? 1 : 0;

@@ -108,6 +108,7 @@ class SphGpuSingle {
   // mDBC: the current vectors particle -> ghost node by idp (the extra data of a PART)
   unsigned DownloadNormals(float* out, unsigned cap, int* usenormalsft);
   void DownloadInteraction(SphInterOut& out);
+  void DownloadExt(SphExtOut& out, bool keep_tau);
   void CountPairs(uint64_t out[6]);
   void SetTiming(bool on);
   void SetTimingPhases(unsigned mask);

@@ -75,7 +75,7 @@
 extern "C" {
 #endif
 
-#define SPH_ABI_VERSION 17
+#define SPH_ABI_VERSION 18
 
 typedef enum {
   SPH_OK = 0,
@@ -298,6 +298,15 @@ typedef struct SphInterOut {
   float viscdtmax, velmax, acemax;
 } SphInterOut;
 
+/* The two outputs of an interaction with Laminar+SPS viscosity and/or shifting that no other
+ * call shows (sph_download_ext): the shifting sums (JSphCpu.cpp:743-750) and the SPS stress
+ * tensor of ComputeSpsTau (JSphCpu.cpp:929-954).  Rows in device order (sph_download_particles);
+ * boundary rows are 0. */
+typedef struct SphExtOut {
+  float* shiftposfs;  /* host [np][4]: {sum m2/rho2 fr (x,y,z), -sum m2/rho2 dr.fr}; x = FLT_MAX where frozen; NULL to skip */
+  float* tau;         /* host [np][6]: xx,xy,xz,yy,yz,zz of the tensor THIS interaction computed; NULL to skip */
+} SphExtOut;
+
 typedef struct SphSolver SphSolver;
 
 /* ---- library ----------------------------------------------------------- */
@@ -347,6 +356,18 @@ int sph_solver_dt_trace(SphSolver* s, double* out, uint32_t cap, uint32_t* count
 /* ---- data out ------------------------------------------------------------ */
 int sph_download_particles(SphSolver* s, SphParticlesHost* out);
 int sph_download_interaction(SphSolver* s, SphInterOut* out);
+/* A diagnostic: one Interaction_Forces(1) on the current state, as sph_download_interaction
+ * runs it, and the shifting sums and / or the SPS stress tensor it computed.
+ *   keep_tau = 0: the state's SPS tensor stays the one it was (an inspection, as
+ *                 sph_download_interaction leaves it);
+ *   keep_tau != 0: the tensor just computed becomes the state's, as a step's interaction leaves
+ *                 it: a following sph_download_interaction is then the second interaction at
+ *                 unchanged positions and velocities, reading this tensor.
+ * Either way the ViscDt and AceMax accumulators are reset at the end, so the next interaction
+ * starts as after a step.  SPH_ERR_UNSUPPORTED on a slab (or a slab group's member),
+ * SPH_ERR_STATE when a requested array belongs to an option the case does not have (tau
+ * without Laminar+SPS, shiftposfs without shifting), SPH_ERR_ARG on NULL s / out. */
+int sph_download_ext(SphSolver* s, SphExtOut* out, int keep_tau);
 
 /* ---- measurement ----------------------------------------------------------- */
 /* Pair counts of one interaction pass (JDsPips): checked & real pairs for
