@@ -640,6 +640,70 @@ class HostParticles:
         )
 
 
+# ---- inlet/outlet zones (sphcore.h: sph_solver_set_inout) ----------------------------------------
+SPH_MAX_INOUTZONES = 16
+SPH_FLAG_INOUT_FULL = 256
+
+
+class SphInOutZoneDef(C.Structure):
+    _fields_ = [
+        ("direction", C.c_double * 3), ("plane", C.c_float * 4), ("veldata", (C.c_float * 4) * 2),
+        ("boxlimitmin", C.c_float * 3), ("boxlimitmax", C.c_float * 3), ("width", C.c_float), ("zsurf", C.c_float),
+        ("cfgzone", C.c_uint32), ("cfgupdate", C.c_uint32), ("layers", C.c_uint32), ("point0", C.c_uint32),
+        ("npoints", C.c_uint32), ("pad", C.c_uint32),
+    ]
+
+
+class SphInOutDef(C.Structure):
+    _fields_ = [
+        ("nzones", C.c_uint32), ("useboxlimit", C.c_int32), ("extrapolatemode", C.c_int32),
+        ("codenewpart", C.c_uint32), ("determlimit", C.c_float), ("freelimitmin", C.c_float * 3),
+        ("freelimitmax", C.c_float * 3), ("resize_plus0", C.c_uint32), ("capacity", C.c_uint32), ("pad", C.c_uint32),
+    ]
+
+
+class SphInOutStats(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("idmax", C.c_uint32), ("capacity", C.c_uint32), ("pad", C.c_uint32),
+                ("created", C.c_uint64), ("removed", C.c_uint64)]
+
+
+def inout_arrays(inout: dict, capacity: int = 0):
+    """(SphInOutDef, SphInOutZoneDef[], points [n][3]) of a case's zones (XmlCase.inout); capacity:
+    the explicit particle capacity (0: the particles + NpResizePlus0)."""
+    zones = inout["zones"]
+    d = SphInOutDef()
+    d.nzones = len(zones)
+    d.useboxlimit = int(bool(inout["useboxlimit"]))
+    d.extrapolatemode = int(inout["extrapolatemode"])
+    d.codenewpart = int(inout["codenewpart"])
+    d.determlimit = float(inout["determlimit"])
+    for i in range(3):
+        d.freelimitmin[i] = float(inout["freelimitmin"][i])
+        d.freelimitmax[i] = float(inout["freelimitmax"][i])
+    d.resize_plus0 = int(inout["npresizeplus0"])
+    d.capacity = int(capacity)
+    arr = (SphInOutZoneDef * max(1, len(zones)))()
+    pts, p0 = [], 0
+    for i, z in enumerate(zones):
+        a = arr[i]
+        for k in range(3):
+            a.direction[k] = float(z["direction"][k])
+            a.boxlimitmin[k] = float(z["boxlimitmin"][k])
+            a.boxlimitmax[k] = float(z["boxlimitmax"][k])
+        for k in range(4):
+            a.plane[k] = float(z["plane"][k])
+            a.veldata[0][k] = float(z["veldata"][0][k])
+            a.veldata[1][k] = float(z["veldata"][1][k])
+        a.width, a.zsurf = float(z["width"]), float(z["zsurf"])
+        a.cfgzone, a.cfgupdate, a.layers = int(z["cfgzone"]), int(z["cfgupdate"]), int(z["layers"])
+        zp = np.asarray(z["points"], np.float64)[np.asarray(z["pointsinit"], bool)]
+        a.point0, a.npoints = p0, len(zp)
+        p0 += len(zp)
+        pts.append(zp)
+    points = np.ascontiguousarray(np.concatenate(pts).reshape(-1, 3), np.float64)
+    return d, arr, points
+
+
 def check_struct_sizes() -> dict:
     return {
         "SphCaseDef": C.sizeof(SphCaseDef),
@@ -659,4 +723,7 @@ def check_struct_sizes() -> dict:
         "SphDampingDef": C.sizeof(SphDampingDef),
         "SphDampingDerived": C.sizeof(SphDampingDerived),
         "SphDemDef": C.sizeof(SphDemDef),
+        "SphInOutZoneDef": C.sizeof(SphInOutZoneDef),
+        "SphInOutDef": C.sizeof(SphInOutDef),
+        "SphInOutStats": C.sizeof(SphInOutStats),
     }

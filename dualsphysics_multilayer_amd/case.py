@@ -799,6 +799,108 @@ class PeriodicChannelCase:
 
 
 @dataclass
+class InOutChannelCase:
+    """An open channel: the lattice of ``PeriodicChannelCase`` without periodic boundaries (floor
+    k = 0, fluid k in [1, depth] moving with `vel0`; 3-D: the walls j = 0 and j = ny, 2-D: the
+    plane y = 0), an inlet zone whose points lie at x = -dp (direction +x) and an outlet zone
+    whose points lie at x = nx dp (direction -x), both with `layers` layers, and the
+    ``<simulationdomain>`` widened by (layers + 1) dp in x at both ends so that the zones and the
+    layer beyond them (JSphInOutPoints::CheckPoints) lie inside the map.
+
+    `zones`: two dicts (inlet, outlet) with the keys of an ``<inoutzone>``: ``refilling``,
+    ``inputtreatment``, ``velocity`` (None: extrapolated; (v,): uniform; (v, v2, z, z2): linear;
+    (v, v2, v3, z, z2, z3): parabolic), ``rhop`` (imposerhop mode 0/1/2), ``zsurf`` (None: no
+    <imposezsurf>) and ``remove``.  `extra`: further PeriodicChannelCase arguments."""
+
+    dp: float
+    nx: int
+    ny: int
+    nz: int
+    depth: int
+    zones: list
+    vel0: tuple = (0.0, 0.0, 0.0)
+    data2d: bool = False
+    step_algorithm: int = STEP_VERLET
+    tdensity: int = DDT_DDT2
+    layers: int = 4
+    determlimit: float = 1e3
+    extrapolatemode: int = 1
+    useboxlimit: bool = True
+    memoryresize: tuple = (2.0, 4.0)
+    extra: dict = field(default_factory=dict)
+
+    def __post_init__(self) -> None:
+        if len(self.zones) != 2:
+            raise ValueError("InOutChannelCase takes the inlet's and the outlet's zone")
+        self.base = PeriodicChannelCase(self.dp, self.nx, self.ny, self.nz, self.depth, {}, vel0=self.vel0,
+                                        ywalls=not self.data2d, data2d=self.data2d,
+                                        step_algorithm=self.step_algorithm, tdensity=self.tdensity, **self.extra)
+        for k in ("pos", "npb", "np", "idp", "vel", "rhop", "rhop0", "gamma", "gravity", "timemax", "timeout"):
+            setattr(self, k, getattr(self.base, k))
+        self.xmargin = (self.layers + 1) * self.dp
+
+    h = property(lambda self: self.base.h)
+    cteb = property(lambda self: self.base.cteb)
+    mass = property(lambda self: self.base.mass)
+
+    def map_limits(self) -> tuple[np.ndarray, np.ndarray]:
+        """MapRealPosMin/Max: border h BORDER_MAP, posmin x "default - m", posmax x "default + m"
+        and z "default + 50%" (JSph::ResizeMapLimits)."""
+        border = float(np.float32(self.h)) * BORDER_MAP
+        m = float("%.10g" % self.xmargin)
+        rmin, rmax = self.pos.min(axis=0) - border, self.pos.max(axis=0) + border
+        dmin = rmin - np.array([m, 0.0, 0.0])
+        dmax = rmax + (rmax - rmin) * np.array([0.0, 0.0, 0.5]) + np.array([m, 0.0, 0.0])
+        return dmin, dmax
+
+    def zone_xml(self, z: dict, inlet: bool) -> list:
+        dp = self.dp
+        x, dx = (-dp, 1) if inlet else (self.nx * dp, -1)
+        lines = ["<inoutzone>", '<refilling value="%d"/>' % z.get("refilling", 0),
+                 '<inputtreatment value="%d"/>' % z.get("inputtreatment", 0), '<layers value="%d"/>' % self.layers]
+        if self.data2d:
+            lines += ['<zone2d><line><point x="%.10g" z="%.10g"/><point2 x="%.10g" z="%.10g"/>'
+                      '<direction x="%d" z="0"/></line></zone2d>' % (x, dp, x, self.depth * dp, dx)]
+        else:
+            lines += ['<zone3d><box><point x="%.10g" y="%.10g" z="%.10g"/><size x="0" y="%.10g" z="%.10g"/>'
+                      '<direction x="%d" y="0" z="0"/></box></zone3d>'
+                      % (x, dp, dp, (self.ny - 2) * dp, (self.depth - 1) * dp, dx)]
+        v = z.get("velocity")
+        if v is None:
+            lines.append('<imposevelocity mode="2"/>')
+        else:
+            tag = {1: "velocity", 4: "velocity2", 6: "velocity3"}[len(v)]
+            names = {1: ("v",), 4: ("v", "v2", "z", "z2"), 6: ("v", "v2", "v3", "z", "z2", "z3")}[len(v)]
+            lines.append('<imposevelocity mode="0"><%s %s/></imposevelocity>'
+                         % (tag, " ".join('%s="%.10g"' % (n, x_) for n, x_ in zip(names, v))))
+        lines.append('<imposerhop mode="%d"/>' % z.get("rhop", 0))
+        if z.get("zsurf") is not None:
+            lines.append('<imposezsurf mode="0"><zsurf value="%.10g"/><remove value="%s"/></imposezsurf>'
+                         % (z["zsurf"], "true" if z.get("remove") else "false"))
+        lines.append("</inoutzone>")
+        return lines
+
+    def xml(self, app: str = "dualsphysics_multilayer_amd") -> str:
+        text = self.base.xml(app)
+        m = "%.10g" % self.xmargin
+        old = '<posmin x="default" y="default" z="default"/><posmax x="default" y="default" z="default + 50%"/>'
+        new = ('<posmin x="default - %s" y="default" z="default"/>'
+               '<posmax x="default + %s" y="default" z="default + 50%%"/>' % (m, m))
+        assert old in text
+        sp = ["<special>", "<inout>", '<memoryresize size0="%.10g" size="%.10g"/>' % tuple(self.memoryresize),
+              '<useboxlimit value="%s"/>' % ("true" if self.useboxlimit else "false"),
+              '<determlimit value="%.10g"/>' % self.determlimit,
+              '<extrapolatemode value="%d"/>' % self.extrapolatemode]
+        sp += self.zone_xml(self.zones[0], True) + self.zone_xml(self.zones[1], False)
+        sp += ["</inout>", "</special>"]
+        return text.replace(old, new).replace("</execution>", "\n".join(sp) + "\n</execution>")
+
+    def write(self, dirname: str, name: str = "CaseInOut") -> str:
+        """Case<name>.xml and .bi4 into dirname; returns the case path without extension."""
+        return PeriodicChannelCase.write(self, dirname, name)
+
+
+@dataclass
 class BlocksCase:
     """A tank (floor and side walls) with a shallow pool at one end and three floating boxes of
     different materials over the dry part of the floor, for the DEM collisions of RigidAlgorithm=2

@@ -52,6 +52,10 @@ from ._abi import (
     floating_array,
     motion_arrays,
     motion_tree_arrays,
+    SphInOutDef,
+    SphInOutStats,
+    SphInOutZoneDef,
+    inout_arrays,
 )
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -123,6 +127,8 @@ EXPORTED_SYMBOLS = (
     "sph_solver_set_damping",
     "sph_accinput_velocities",
     "sph_damping_derive",
+    "sph_solver_set_inout",
+    "sph_solver_inout_stats",
 )
 
 
@@ -220,6 +226,9 @@ def load_library(path: str = LIB_PATH):
     L.sph_solver_set_damping.argtypes = [vp, C.c_uint32, C.POINTER(SphDampingDef)]
     L.sph_accinput_velocities.argtypes = [C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sph_damping_derive.argtypes = [C.POINTER(SphDampingDef), C.c_uint32, C.POINTER(SphDampingDerived)]
+    L.sph_solver_set_inout.argtypes = [vp, C.POINTER(SphInOutDef), C.POINTER(SphInOutZoneDef), C.POINTER(C.c_double),
+                                       C.c_uint32]
+    L.sph_solver_inout_stats.argtypes = [vp, C.POINTER(SphInOutStats)]
     if L.sph_abi_version() != SPH_ABI_VERSION:
         raise SphError(3, "ABI version mismatch")
     _lib = L
@@ -302,6 +311,9 @@ class SphGpuSingle:
             self.set_accinputs(case.accinputs)
         if getattr(case, "damping", None):
             self.set_damping(case.damping)
+        # <special><inout> (JSphCpuSingle::InOutInit): the zones and their initial particles
+        if getattr(case, "inout", None):
+            self.set_inout(case.inout, getattr(case, "inout_capacity", 0))
         if not getattr(case, "has_bodies", False):
             return
         # a restart sets the PART time first: the motion program is advanced to it
@@ -353,6 +365,21 @@ class SphGpuSingle:
         """Damping zones (XmlCase.damping dicts, _abi.damping_array) applied after every step's last
         update; once, before the first step."""
         _check(load_library().sph_solver_set_damping(self._h, len(damping), damping_array(damping)))
+
+    def set_inout(self, inout: dict, capacity: int = 0) -> None:
+        """Inlet/outlet zones (XmlCase.inout) with their initial particles; once, before the first
+        step.  capacity: the particle capacity (0: the particles + NpResizePlus0)."""
+        d, zones, points = inout_arrays(inout, capacity)
+        _check(load_library().sph_solver_set_inout(self._h, C.byref(d), zones,
+                                                   points.ctypes.data_as(C.POINTER(C.c_double)), len(points)))
+        self._inout = True
+
+    def inout_stats(self) -> dict:
+        """The zones' counters: inout particles now, IdMax, the particle capacity, particles
+        created and removed by the zones so far."""
+        out = SphInOutStats()
+        _check(load_library().sph_solver_inout_stats(self._h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k, _ in SphInOutStats._fields_ if k != "pad"}
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -411,7 +438,8 @@ class SphGpuSingle:
         return out
 
     def particles(self) -> dict:
-        hp = HostParticles(self.case.np)
+        # (with inlet/outlet zones the particle count follows the device's)
+        hp = HostParticles(self.stats()["np"] if getattr(self, "_inout", False) else self.case.np)
         _check(load_library().sph_download_particles(self._h, C.byref(hp.view)))
         return hp.trimmed(hp.view.n)
 
@@ -551,6 +579,11 @@ def comm_unique_id() -> bytes:
     return bytes(buf)
 
 
+def _no_inout_on_slabs(case) -> None:
+    if getattr(case, "inout", None):
+        raise SphError(7, "inlet/outlet zones are not implemented for slab solvers")
+
+
 class SphGpuSlab(SphGpuSingle):
     """One slab of a domain decomposed over x (axis 0) or y (axis 1), one process per GPU
     over RCCL.
@@ -565,6 +598,7 @@ class SphGpuSlab(SphGpuSingle):
         "shm": comm_id = the shared-memory segment name ("/...", same on every rank; ranks of
         one node without RCCL, e.g. several on one GPU), slot_bytes per mailbox."""
         L = load_library()
+        _no_inout_on_slabs(case)
         self.case = case
         self._cdef = SphCaseDef.from_dict(case.case_def())
         init = case_particles(case)
@@ -607,6 +641,7 @@ class SphSlabGroup:
 
     def __init__(self, case, bounds, devices=None, axis: int = 0):
         L = load_library()
+        _no_inout_on_slabs(case)
         bounds = np.ascontiguousarray(bounds, np.int32)
         n = len(bounds) - 1
         devices = np.ascontiguousarray(devices if devices is not None else np.zeros(n), np.int32)

@@ -41,6 +41,15 @@ int guard(F&& f) {
       return SPH_ERR_STATE;                                                         \
     }                                                                               \
   } while (0)
+// a solver with inlet/outlet zones is stepped by sph_solver_run only (InOutComputeStep belongs
+// to the end-of-step divide)
+#define NOT_INOUT(s)                                                                                   \
+  do {                                                                                                 \
+    if ((s)->impl->InOut()) {                                                                          \
+      g_last_error = "inlet/outlet zones: the phase-level calls are not supported (sph_solver_run)"; \
+      return SPH_ERR_UNSUPPORTED;                                                                      \
+    }                                                                                                  \
+  } while (0)
 #define NEED(x)                                   \
   do {                                            \
     if (!(x)) {                                   \
@@ -80,31 +89,37 @@ int sph_solver_destroy(SphSolver* s) {
 int sph_divide(SphSolver* s) {
   NEED(s);
   NOT_MEMBER(s);
+  NOT_INOUT(s);
   return guard([&] { s->impl->RunCellDivide(); });
 }
 int sph_interaction_forces(SphSolver* s, int interstep) {
   NEED(s && interstep >= 1 && interstep <= 3);
   NOT_MEMBER(s);
+  NOT_INOUT(s);
   return guard([&] { s->impl->Interaction_Forces(interstep); });
 }
 int sph_compute_dt(SphSolver* s, int final_) {
   NEED(s);
   NOT_MEMBER(s);
+  NOT_INOUT(s);
   return guard([&] { s->impl->PhaseDt(final_ != 0); });
 }
 int sph_step_verlet(SphSolver* s) {
   NEED(s);
   NOT_MEMBER(s);
+  NOT_INOUT(s);
   return guard([&] { s->impl->PhaseUpdate(1); });
 }
 int sph_step_symplectic_pre(SphSolver* s) {
   NEED(s);
   NOT_MEMBER(s);
+  NOT_INOUT(s);
   return guard([&] { s->impl->PhaseUpdate(2); });
 }
 int sph_step_symplectic_cor(SphSolver* s) {
   NEED(s);
   NOT_MEMBER(s);
+  NOT_INOUT(s);
   return guard([&] { s->impl->PhaseUpdate(3); });
 }
 int sph_solver_run(SphSolver* s, uint32_t nsteps) {
@@ -458,6 +473,17 @@ int sph_normals_write(const char* path, const char* case_name, double dp, double
 int sph_bi4_rewrite(const char* src, const char* dst) {
   NEED(src && dst);
   return guard([&] { sphx::bi4_rewrite(src, dst); });
+}
+
+int sph_solver_set_inout(SphSolver* s, const SphInOutDef* def, const SphInOutZoneDef* zones, const double* points,
+                         uint32_t npoints) {
+  NEED(s && def && zones && points);
+  NOT_MEMBER(s);
+  return guard([&] { s->impl->SetInOut(*def, zones, points, npoints); });
+}
+int sph_solver_inout_stats(SphSolver* s, SphInOutStats* out) {
+  NEED(s && out);
+  return guard([&] { *out = s->impl->InOutStats(); });
 }
 
 }  // extern "C"

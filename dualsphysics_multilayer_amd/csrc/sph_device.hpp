@@ -222,6 +222,10 @@ struct DevScalars {
   // (JSphCpuSingle.cpp:678; DtIni before the first, a restart's PART value); Symplectic: the
   // interactions take dt/2 and dt of the step in flight (:700,709) and this holds dt after it.
   double demdtforce;
+  // inlet/outlet zones (sph_inout.hip): IdMax, the inout particles after the last parts-data
+  // pass, the particles created and removed by the zones so far, the extrapolation list's length
+  unsigned io_idmax, io_count, io_nlist, io_pad;
+  unsigned long long io_created, io_removed;
 };
 // RED_VISCETA: NN max effective viscosity (ViscEtaDtMax, JSphCpuSingle.cpp:633 in the v5.0 solver)
 constexpr int RED_VELMAX2 = 0, RED_ACEMAX2 = 1, RED_VISCDT = 2, RED_VISCETA = 3, RED_SLOTS = 64;
@@ -243,7 +247,10 @@ constexpr unsigned ERR_HALO = ERR_HALO_NODE | ERR_HALO_FACE | ERR_HALO_MISS | ER
 // the periodic duplicates of a divide did not fit the particle capacity (sph_periodic.hip):
 // nothing is written past it, the run stops at this step (SPH_FLAG_PERIODIC_FULL)
 constexpr unsigned ERR_PERI_FULL = 128u;
-constexpr unsigned ERR_FATAL = ERR_DT_NAN | ERR_BOUNDOUT | ERR_HALO | ERR_PERI_FULL;
+// the new inlet particles of a step did not fit the particle capacity (sph_inout.hip): none is
+// created, the run stops at this step (SPH_FLAG_INOUT_FULL)
+constexpr unsigned ERR_INOUT_FULL = 256u;
+constexpr unsigned ERR_FATAL = ERR_DT_NAN | ERR_BOUNDOUT | ERR_HALO | ERR_PERI_FULL | ERR_INOUT_FULL;
 __device__ __forceinline__ bool halted(const DevScalars* sc) { return (sc->error_flags & ERR_FATAL) != 0u; }
 
 // Wave-level max of a non-negative float, then one atomicMax per wave into a slot

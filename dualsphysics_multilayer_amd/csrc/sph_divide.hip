@@ -381,17 +381,6 @@ __device__ __forceinline__ void gather_store(const GatherArgs& a, unsigned i,
   // double pow, and -ffast-math makes rhop/rhop0 a product with 1/rhop0.  For an
   // integer gamma the double power is formed by squaring (<= 4 roundings at 1e-16,
   // far below the float rounding of the result).
-  auto powg = [](double x, int ig, double g) -> double {
-    if (ig > 0) {  // integer gamma (7 in every case here): exact squaring in double
-      double r = 1.0, b = x;
-      for (int e = ig; e; e >>= 1) {
-        if (e & 1) r *= b;
-        b *= b;
-      }
-      return r;
-    }
-    return pow(x, g);
-  };
   if (a.phase_eos) {
     // ComputePress_NN (JSphCpu_Tensors.cpp:40-62 of the v5.0 solver): the phase's rho0, CteB
     // and gamma for fluid particles, the case's for the boundary, in float arithmetic
@@ -406,10 +395,9 @@ __device__ __forceinline__ void gather_store(const GatherArgs& a, unsigned i,
       ig = int(e.w);
     }
     const float r = vr.w / rho0;
-    a.press[i] = cteb * (float(powg(double(r), ig, double(gam))) - 1.0f);
+    a.press[i] = cteb * (float(pow_gamma(double(r), ig, double(gam))) - 1.0f);
   } else {
-    const double xr = double(vr.w * a.ovrhopzero);
-    a.press[i] = float(double(a.cteb) * (powg(xr, a.igamma, double(a.gamma)) - 1.0));
+    a.press[i] = eos_press(a.cteb, a.ovrhopzero, a.gamma, a.igamma, vr.w);
   }
 }
 
@@ -472,7 +460,7 @@ void launch_gather(hipStream_t stm, unsigned cap, DevScalars* sc, const unsigned
   a.ovrhopzero = K.ovrhopzero;
   a.rhopzero = K.rhopzero;
   a.gamma = K.gamma;
-  a.igamma = (K.gamma == float(int(K.gamma)) && K.gamma >= 1.f && K.gamma <= 16.f) ? int(K.gamma) : 0;
+  a.igamma = integer_gamma_of(K.gamma);
   a.dcc = K.domcellcode;
   a.withm1 = withm1;
   a.withpre = withpre;
@@ -1204,7 +1192,7 @@ void launch_divide_inc(hipStream_t stm, unsigned cap, DevScalars* sc, const Part
   a.ovrhopzero = K.ovrhopzero;
   a.rhopzero = K.rhopzero;
   a.gamma = K.gamma;
-  a.igamma = (K.gamma == float(int(K.gamma)) && K.gamma >= 1.f && K.gamma <= 16.f) ? int(K.gamma) : 0;
+  a.igamma = integer_gamma_of(K.gamma);
   a.dcc = K.domcellcode;
   a.withm1 = withm1;
   a.withpre = withpre;
@@ -1280,7 +1268,7 @@ void launch_ghost_scatter(hipStream_t stm, DevScalars* sc, const SlabGhost* rec,
   a.ovrhopzero = K.ovrhopzero;
   a.rhopzero = K.rhopzero;
   a.gamma = K.gamma;
-  a.igamma = (K.gamma == float(int(K.gamma)) && K.gamma >= 1.f && K.gamma <= 16.f) ? int(K.gamma) : 0;
+  a.igamma = integer_gamma_of(K.gamma);
   a.dcc = K.domcellcode;
   a.withm1 = 0;
   a.withpre = 0;

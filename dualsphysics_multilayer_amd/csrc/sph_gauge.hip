@@ -38,14 +38,6 @@ __device__ __forceinline__ double wmax_d(double v) {
   return v;
 }
 
-// int((pos - posmin) / scell) with a defined cast for any input (far outside: no cell).
-__device__ __forceinline__ int cell_of(double d, double scell) {
-  const double c = d / scell;
-  if (!(c == c) || c < -1.0e9) return -1000000000;
-  if (c > 1.0e9) return 1000000000;
-  return int(c);
-}
-
 // nsearch::Init(pos, false, dvd) (JCellSearch_inline.h:54-69); false when the position has no
 // cell in the domain (the reference reads out of range there).
 struct NgBox {

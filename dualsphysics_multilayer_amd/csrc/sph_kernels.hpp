@@ -33,6 +33,38 @@ __device__ __forceinline__ double nc(double x) {
   return x;
 }
 
+// x^gamma in double as the divide's EOS forms it: an integer gamma (ig > 0) by exact squaring
+// (<= 4 roundings at 1e-16, far below the float rounding of the result), else pow.
+__device__ __forceinline__ double pow_gamma(double x, int ig, double g) {
+  if (ig > 0) {
+    double r = 1.0, b = x;
+    for (int e = ig; e; e >>= 1) {
+      if (e & 1) r *= b;
+      b *= b;
+    }
+    return r;
+  }
+  return pow(x, g);
+}
+// gamma as a small positive integer, else 0.
+__host__ __device__ __forceinline__ int integer_gamma_of(float gamma) {
+  return (gamma == float(int(gamma)) && gamma >= 1.f && gamma <= 16.f) ? int(gamma) : 0;
+}
+// The single-phase press of a particle as the divide stores it (PreInteractionVars_Forces,
+// JSphCpu.cpp:451-453; FunSphEos.h:37-47): the reference binary's double pow, with rhop/rhop0 as
+// a float product with 1/rhop0.
+__device__ __forceinline__ float eos_press(float cteb, float ovrhopzero, float gamma, int igamma, float rhop) {
+  const double xr = double(rhop * ovrhopzero);
+  return float(double(cteb) * (pow_gamma(xr, igamma, double(gamma)) - 1.0));
+}
+// int((pos - posmin) / scell) with a defined cast for any input (far outside: no cell).
+__device__ __forceinline__ int cell_of(double d, double scell) {
+  const double c = d / scell;
+  if (!(c == c) || c < -1.0e9) return -1000000000;
+  if (c > 1.0e9) return 1000000000;
+  return int(c);
+}
+
 // JSphCpu::UpdatePos (JSphCpu.cpp:1240-1293), single domain.  PERI (a case with periodic
 // boundaries, P set): a particle that left the real map is wrapped on each periodic axis by the
 // whole Peri?inc vector, only the other axes can mark it OUTPOS, and the cell is taken from
@@ -478,6 +510,10 @@ void launch_sym_pre(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst&
 void launch_sym_cor(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, const float4* arace, PartArrays a,
                     DivGrid g, const float4* shiftpos = nullptr, const IncDivScratch* cls = nullptr,
                     const PackArgs* pk = nullptr, const PeriConst* peri = nullptr);
+// The updates of a case with inlet/outlet zones (kind 0 Verlet, 1 Symplectic predictor, 2
+// corrector): the inout particles keep their velocity and density (sph_step.hip k_update_inout).
+void launch_update_inout(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, int kind, bool euler,
+                         const float4* arace, PartArrays a, DivGrid g);
 
 // ---- periodic boundaries (sph_periodic.hip) ----
 // JSphCpuSingle::RunPeriodic (JSphCpuSingle.cpp:361-431) at the top of a divide: the duplicates

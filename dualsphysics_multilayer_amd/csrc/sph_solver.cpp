@@ -11,6 +11,7 @@
 #include <chrono>
 #include <exception>
 #include <thread>
+#include <unordered_map>
 
 namespace sphx {
 
@@ -844,6 +845,11 @@ void SphGpuSingle::AllocParticles(unsigned cap) {
   // slab pack tile counts: tilecnt[7][ntiles] (ghost L/R, migrant L/R, staying, face ghosts L/R; sph_slab.hip)
   packtiles_ = (unsigned*)dmalloc(PK_TILECNT_BYTES(n));
   if (peri_) periscan_ = (unsigned*)dmalloc(4 * peri_scan_words(cap));
+  if (inout_) {
+    ioscan_ = (unsigned*)dmalloc(4 * inout_scan_words(cap));
+    ionewiz_ = (unsigned char*)dmalloc(n);
+    iolist_ = (unsigned*)dmalloc(4 * n);
+  }
   cap_ = cap;
 }
 
@@ -1040,6 +1046,8 @@ void SphGpuSingle::UploadNormals(const SphCaseDef& cdef, const SphParticlesHost&
 
 // Restart: TimeStep and SymplecticDtPre of the loaded PART (JSph::InitRun, JSph.cpp:2094-2106).
 void SphGpuSingle::SetTime(double time, double symdtpre) {
+  if (inout_)  // JSphCpuSingle_InOut.cpp:76
+    throw SphError(SPH_ERR_UNSUPPORTED, "Simulation restart not allowed when Inlet/Outlet is used.");
   if (motion_) throw SphError(SPH_ERR_STATE, "set the restart time before the motion (it is advanced to that time)");
   UploadFloatingTables();  // the floating tables' lookups start over (a restart's new JLinearValues)
   Sync();
@@ -1383,6 +1391,9 @@ void SphGpuSingle::RunCellDivide() {
   const bool withm1 = (step_algorithm_ == SPH_STEP_VERLET);
   // RunPeriodic before every divide, the in-step one of Symplectic included (JSphCpuSingle.cpp:444)
   if (peri_) launch_run_periodic(stream, cap_, sc_, P_, K, cur_, withm1, havepre_, periscan_);
+  // InOutComputeStep at the end-of-step divide (JSphCpuSingle_InOut.cpp:146-210): the zones' rules
+  // and the new inlet particles behind np
+  if (inout_ && io_pass_ == 2) launch_inout_step(stream, cap_, sc_, iodev_, K, cur_, ioscan_, ionewiz_);
   // Items (each build also zeroes its queues).  With the overlap a slab cuts its rows where
   // the stencil (scelldiv columns) stops reaching a ghost column: the interior list runs
   // while the ghost records are in flight, the face list (items of <= scelldiv columns) after
@@ -1462,6 +1473,9 @@ void SphGpuSingle::RunCellDivide() {
     }
   }
   if (nftp_) launch_ft_ridp(stream, cap_, sc_, cur_, casenpb_, nftp_, ftridp_, K, G);
+  // InOutUpdatePartsData after it (JSphCpuSingle_InOut.cpp:216-217, 228-255)
+  if (inout_ && io_pass_)
+    launch_inout_parts(stream, cap_, sc_, iodev_, ioh_, K, G, cur_, begincell_, press_, iolist_, withm1);
   TimedEnd(2);
   if (turn) transport_->turn_done(SlabTransport::TURN_DIVIDE, stream);
 }
@@ -1604,6 +1618,11 @@ void SphGpuSingle::Interaction_Forces(int interstep) {
     check_hip(hipMemsetAsync(&sc_->red[RED_ACEMAX2][0], 0, 4 * RED_SLOTS, stream), "reset acemax");
     launch_peri_acemax(stream, cap_, sc_, cur_.code, arace_);
   }
+  if (inout_) {
+    // AceMax over the normal particles that are not inout (ComputeAceMax, JSphCpuSingle.cpp:584-605)
+    check_hip(hipMemsetAsync(&sc_->red[RED_ACEMAX2][0], 0, 4 * RED_SLOTS, stream), "reset acemax");
+    launch_inout_acemax(stream, cap_, sc_, cur_.code, arace_);
+  }
   TimedEnd(0);
   if (turn && fold_turn_ >= 0) {  // the next DtVariable's fold, inside this slab's turn
     launch_fold_maxima(stream, sc_, folded_, fold_turn_ != 0);
@@ -1705,8 +1724,10 @@ void SphGpuSingle::ComputeVerlet() {
   verletstep_++;
   const bool euler = !(verletstep_ < C.verlet_steps);
   const UpdateFuse fu = FuseUpdate(false);
-  launch_verlet(stream, cap_, sc_, K, euler, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk,
-                peri_ ? &P_ : nullptr);
+  if (inout_) launch_update_inout(stream, cap_, sc_, K, 0, euler, arace_, cur_, G);
+  else
+    launch_verlet(stream, cap_, sc_, K, euler, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk,
+                  peri_ ? &P_ : nullptr);
   if (euler) verletstep_ = 0;
   std::swap(cur_.velrhop, cur_.velrhopm1);
   TimedEnd(1);
@@ -1721,7 +1742,8 @@ void SphGpuSingle::ComputeSymplecticPre() {
   std::swap(cur_.velrhop, cur_.velrhoppre);
   havepre_ = true;
   const UpdateFuse fu = FuseUpdate(true);
-  launch_sym_pre(stream, cap_, sc_, K, arace_, cur_, G, fu.cls, fu.pk, peri_ ? &P_ : nullptr);
+  if (inout_) launch_update_inout(stream, cap_, sc_, K, 1, false, arace_, cur_, G);
+  else launch_sym_pre(stream, cap_, sc_, K, arace_, cur_, G, fu.cls, fu.pk, peri_ ? &P_ : nullptr);
   TimedEnd(1);
   UpdateTurn(false);
 }
@@ -1730,8 +1752,10 @@ void SphGpuSingle::ComputeSymplecticCorr() {
   UpdateTurn(true);
   TimedBegin(1);
   const UpdateFuse fu = FuseUpdate(false);
-  launch_sym_cor(stream, cap_, sc_, K, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk,
-                 peri_ ? &P_ : nullptr);
+  if (inout_) launch_update_inout(stream, cap_, sc_, K, 2, false, arace_, cur_, G);
+  else
+    launch_sym_cor(stream, cap_, sc_, K, arace_, cur_, G, shift_ ? shiftpos_ : nullptr, fu.cls, fu.pk,
+                   peri_ ? &P_ : nullptr);
   havepre_ = false;
   TimedEnd(1);
   UpdateTurn(false);
@@ -1764,7 +1788,9 @@ void SphGpuSingle::ComputeStep() {
   if (ndamp_) RunDamping();  // after the last update and RunFloating (JSphCpuSingle.cpp:683,717)
   if (gauges_.ng) RunGauges();  // at TimeStep + stepdt, before the motion and the divide (JSphCpuSingle.cpp:1095)
   if (nmotobj_) RunMotion();
+  io_pass_ = inout_ ? 2 : 0;  // InOutComputeStep in place of the plain divide (JSphCpuSingle.cpp:1097)
   RunCellDivide();
+  io_pass_ = 0;
 }
 
 void SphGpuSingle::PhaseDt(bool final_) {
@@ -2026,6 +2052,7 @@ void SphGpuSingle::RunGauges() {
 void SphGpuSingle::SetGauges(unsigned n, const SphGaugeDef* defs, unsigned record_capacity) {
   if (slab()) throw SphError(SPH_ERR_UNSUPPORTED, "gauges run on a single domain only (not on slabs)");
   if (peri_) throw SphError(SPH_ERR_UNSUPPORTED, "gauges with periodic boundaries are not implemented");
+  if (inout_) throw SphError(SPH_ERR_UNSUPPORTED, "gauges with inlet/outlet zones are not implemented");
   if (nn_) throw SphError(SPH_ERR_UNSUPPORTED, "gauges with NN multiphase are not implemented");
   if (stepped_ || gauges_.ng) throw SphError(SPH_ERR_STATE, "the gauges are configured once, before the first step");
   if (!n || !defs) throw SphError(SPH_ERR_ARG, "no gauges");
@@ -2193,6 +2220,7 @@ void SphGpuSingle::SetMotion(unsigned nobj, unsigned nmov, const SphMotionMov* m
 void SphGpuSingle::SetMotionTree(unsigned nnode, const SphMotionObj* nodes, unsigned nmov, const SphMotionMov* movs,
                                  unsigned nevt, const SphMotionEvent* evts, unsigned nrows, const double* rows) {
   if (peri_) throw SphError(SPH_ERR_UNSUPPORTED, "moving boundaries with periodic boundaries are not implemented");
+  if (inout_) throw SphError(SPH_ERR_UNSUPPORTED, "moving boundaries with inlet/outlet zones are not implemented");
   if (stepped_ || motion_) throw SphError(SPH_ERR_STATE, "the motion is configured once, before the first step");
   if (!nnode || nnode > unsigned(MOT_MAXOBJ)) throw SphError(SPH_ERR_UNSUPPORTED, "number of motion objects out of range");
   if ((nmov && !movs) || (nevt && !evts) || (nrows && !rows)) throw SphError(SPH_ERR_ARG, "motion arrays missing");
@@ -2327,6 +2355,7 @@ void SphGpuSingle::SetMotionTree(unsigned nnode, const SphMotionObj* nodes, unsi
 // JSph::LoadCaseConfig floating objects (JSph.cpp:1046-1100).
 void SphGpuSingle::SetFloatings(unsigned nft, const SphFloatingDef* defs, double ftpause) {
   if (peri_) throw SphError(SPH_ERR_UNSUPPORTED, "floating bodies with periodic boundaries are not implemented");
+  if (inout_) throw SphError(SPH_ERR_UNSUPPORTED, "floating bodies with inlet/outlet zones are not implemented");
   if (stepped_ || ftbodies_) throw SphError(SPH_ERR_STATE, "the floating bodies are configured once, before the first step");
   if (!nft || !defs) throw SphError(SPH_ERR_ARG, "no floating bodies");
   if (nn_) {
@@ -2544,6 +2573,211 @@ unsigned SphGpuSingle::Floatings(SphFloatingState* out, unsigned cap) {
   return unsigned(nftbodies_);
 }
 
+// ---- inlet/outlet zones (sph_inout.hip) --------------------------------------------------------
+// JSphCpuSingle::InOutInit (JSphCpuSingle_InOut.cpp:72-137).
+void SphGpuSingle::SetInOut(const SphInOutDef& def, const SphInOutZoneDef* zones, const double* points,
+                            unsigned npoints) {
+  if (inout_) throw SphError(SPH_ERR_STATE, "the inlet/outlet zones are already configured");
+  if (stepped_) throw SphError(SPH_ERR_STATE, "configure the inlet/outlet zones before the first step");
+  if (slab()) throw SphError(SPH_ERR_UNSUPPORTED, "inlet/outlet zones are not implemented for slab solvers");
+  const char* bad = nullptr;
+  if (peri_) bad = "periodic boundaries";
+  else if (C.tboundary == SPH_BOUND_MDBC) bad = "mDBC";
+  else if (nn_) bad = "NN multiphase";
+  else if (sps_ || shift_) bad = "Laminar+SPS or shifting";
+  else if (C.symmetry) bad = "Symmetry";
+  else if (nftbodies_ || nmotobj_) bad = "moving boundaries or floating bodies";
+  else if (gauges_.ng) bad = "gauges";
+  else if (C.kernel == SPH_KERNEL_CUBIC) bad = "the Cubic spline kernel";
+  if (bad) throw SphError(SPH_ERR_UNSUPPORTED, std::string("inlet/outlet zones with ") + bad + " are not implemented");
+  if (def.nzones < 1 || def.nzones > unsigned(INOUT_MAXZONES))
+    throw SphError(SPH_ERR_ARG, "Maximum number of inlet/outlet zones has been reached.");
+  if (def.extrapolatemode < 1 || def.extrapolatemode > 3) throw SphError(SPH_ERR_ARG, "invalid extrapolatemode");
+  check_hip(hipSetDevice(device), "hipSetDevice");
+  const SphRunStats st = Stats();
+  if (st.nstep || st.time != 0) throw SphError(SPH_ERR_UNSUPPORTED, "Simulation restart not allowed when Inlet/Outlet is used.");
+  const unsigned n = sc_host_->np;
+  // -- the zone data
+  InOutDev io;
+  std::memset(&io, 0, sizeof(io));
+  io.nzones = int(def.nzones);
+  io.useboxlimit = def.useboxlimit != 0;
+  io.checkfreelimit = (def.useboxlimit != 0 && def.nzones > 2);  // JSphInOut.cpp:807
+  io.extrapmode = def.extrapolatemode;
+  io.determlimit = def.determlimit;
+  io.coefhydro = K.rhopzero * (-K.gravz) / K.cteb;  // JSphInOut.cpp:536
+  io.codenewpart = def.codenewpart;
+  if (CodeType(typecode(def.codenewpart)) != CODE_TYPE_FLUID || CodeIsFluidInout(typecode(def.codenewpart)))
+    throw SphError(SPH_ERR_ARG, "There are not free fluid codes for new particles created during the simulation.");
+  for (int i = 0; i < 3; i++) {
+    io.freemin[i] = def.freelimitmin[i];
+    io.freemax[i] = def.freelimitmax[i];
+  }
+  std::vector<double> npos;  // the initial inout particles (LoadInitPartsData, JSphInOut.cpp:675-695)
+  std::vector<typecode> ncode;
+  for (unsigned c = 0; c < def.nzones; c++) {
+    const SphInOutZoneDef& z = zones[c];
+    InOutZoneDev& d = io.z[c];
+    if ((z.cfgzone & IO_VELM_MASK) != IO_VELM_FIXED && (z.cfgzone & IO_VELM_MASK) != IO_VELM_EXTRAPOLATED)
+      throw SphError(SPH_ERR_UNSUPPORTED, "inlet/outlet zones: variable and interpolated velocities are not implemented");
+    if ((z.cfgzone & IO_RHOP_MASK) > IO_RHOP_EXTRAPOLATED) throw SphError(SPH_ERR_ARG, "inlet/outlet zone: invalid density mode");
+    if (z.cfgupdate & IO_REFILLADVANCED)
+      throw SphError(SPH_ERR_UNSUPPORTED, "inlet/outlet zones: the advanced refilling is not implemented");
+    if (z.layers < 1 || z.layers > 250) throw SphError(SPH_ERR_ARG, "inlet/outlet zone: layers must be in [1, 250]");
+    if (size_t(z.point0) + z.npoints > npoints) throw SphError(SPH_ERR_ARG, "inlet/outlet zone: points out of range");
+    for (int i = 0; i < 4; i++) {
+      d.plane[i] = z.plane[i];
+      d.vel0[i] = z.veldata[0][i];
+    }
+    for (int i = 0; i < 3; i++) {
+      d.dir[i] = float(z.direction[i]);
+      d.boxmin[i] = z.boxlimitmin[i];
+      d.boxmax[i] = z.boxlimitmax[i];
+    }
+    d.width = z.width;
+    d.zsurf = z.zsurf;
+    d.cfgzone = z.cfgzone;
+    d.cfgupdate = z.cfgupdate;
+    for (unsigned layer = 0; layer < z.layers; layer++) {
+      const double f = -C.dp * double(layer);
+      const double dx = z.direction[0] * f, dy = z.direction[1] * f, dz = z.direction[2] * f;
+      for (unsigned q = 0; q < z.npoints; q++) {
+        const double* pt = points + 3 * (size_t(z.point0) + q);
+        const double pp[3] = {pt[0] + dx, pt[1] + dy, pt[2] + dz};
+        for (int i = 0; i < 3; i++) {
+          const double r = pp[i] - C.dom_posmin[i];
+          if (!(r >= 0 && r < C.map_realsize[i]))
+            throw SphError(SPH_ERR_ARG, "Point for inlet conditions is outside the domain.");
+          npos.push_back(pp[i]);
+        }
+        ncode.push_back(typecode(CODE_TYPE_FLUID_INOUT + c));
+      }
+    }
+  }
+  const unsigned nnew = unsigned(ncode.size());
+  if (!nnew) throw SphError(SPH_ERR_ARG, "inlet/outlet zones without initial particles");
+  // -- InitCheckProximity (JSphInOut.cpp:704-775) against the particles held, in device order
+  std::vector<double2> pxy(n);
+  std::vector<double> pz(n);
+  std::vector<typecode> code(n);
+  check_hip(hipMemcpy(pxy.data(), cur_.posxy, 16 * size_t(n), hipMemcpyDeviceToHost), "download posxy");
+  check_hip(hipMemcpy(pz.data(), cur_.posz, 8 * size_t(n), hipMemcpyDeviceToHost), "download posz");
+  check_hip(hipMemcpy(code.data(), cur_.code, 2 * size_t(n), hipMemcpyDeviceToHost), "download code");
+  {
+    const double dist = C.dp * 0.8, dist2 = dist * dist;
+    double lo[3] = {npos[0], npos[1], npos[2]};
+    for (unsigned q = 0; q < nnew; q++)
+      for (int i = 0; i < 3; i++) lo[i] = std::min(lo[i], npos[3 * size_t(q) + i]);
+    for (int i = 0; i < 3; i++) lo[i] -= 2 * dist;
+    auto cellkey = [&](long long cx, long long cy, long long cz) -> unsigned long long {
+      return ((unsigned long long)(cx & 0x1fffff) << 42) | ((unsigned long long)(cy & 0x1fffff) << 21) |
+             (unsigned long long)(cz & 0x1fffff);
+    };
+    std::unordered_map<unsigned long long, std::vector<unsigned>> grid;
+    auto cellof = [&](const double* p, long long c[3]) {
+      for (int i = 0; i < 3; i++) c[i] = (long long)std::floor((p[i] - lo[i]) / dist);
+    };
+    for (unsigned q = 0; q < nnew; q++) {
+      long long c[3];
+      cellof(&npos[3 * size_t(q)], c);
+      grid[cellkey(c[0], c[1], c[2])].push_back(q);
+    }
+    auto near = [&](const double* p, unsigned self) -> bool {
+      long long c[3];
+      cellof(p, c);
+      if (c[0] < -1 || c[1] < -1 || c[2] < -1 || c[0] > 0xfffff || c[1] > 0xfffff || c[2] > 0xfffff) return false;
+      for (long long x = c[0] - 1; x <= c[0] + 1; x++)
+        for (long long y = c[1] - 1; y <= c[1] + 1; y++)
+          for (long long zc = c[2] - 1; zc <= c[2] + 1; zc++) {
+            const auto it = grid.find(cellkey(x, y, zc));
+            if (it == grid.end()) continue;
+            for (unsigned q : it->second) {
+              if (q == self) continue;
+              const double ddx = p[0] - npos[3 * size_t(q)], ddy = p[1] - npos[3 * size_t(q) + 1],
+                           ddz = p[2] - npos[3 * size_t(q) + 2];
+              if (ddx * ddx + ddy * ddy + ddz * ddz <= dist2) return true;
+            }
+          }
+      return false;
+    };
+    unsigned nerr = 0;
+    for (unsigned q = 0; q < nnew; q++) nerr += near(&npos[3 * size_t(q)], q) ? 1u : 0u;
+    for (unsigned p = 0; p < n; p++) {
+      const double pp[3] = {pxy[p].x, pxy[p].y, pz[p]};
+      if (!CodeIsNormal(code[p]) || !near(pp, ~0u)) continue;
+      if (CodeIsFluid(code[p])) code[p] = CodeSetNormal(code[p]) | CODE_OUTIGNORE;  // excluded fluid
+      else nerr++;
+    }
+    if (nerr)
+      throw SphError(SPH_ERR_ARG, "There are inout fluid or boundary particles too close to inout particles.");
+  }
+  // -- the capacity, fixed from here on (every check is done: nothing below refuses the zones)
+  unsigned long long want = def.capacity ? def.capacity : 0ull + n + nnew + def.resize_plus0;
+  if (want < 0ull + n + nnew) throw SphError(SPH_ERR_ARG, "the inout capacity is below the initial particles");
+  if (want >= (1ull << 31)) throw SphError(SPH_ERR_ARG, "The number of particles is too big.");
+  // inout cases take the full sort at every divide, as the reference does with new particles
+  // appended behind np; the update's fused classification goes with the incremental divide
+  inc_ok_ = false;
+  inc_valid_ = false;
+  inout_ = true;
+  ioh_ = io;
+  Grow(n, unsigned(want));
+  check_hip(hipMalloc((void**)&iodev_, sizeof(InOutDev)), "hipMalloc inout zones");
+  allocs_.push_back(iodev_);
+  check_hip(hipMemcpy(iodev_, &io, sizeof(io), hipMemcpyHostToDevice), "upload inout zones");
+  // -- the new particles behind np (cells as JSph::LoadDcellParticles; UpdatePos, :101)
+  std::vector<unsigned> idp(nnew), dcell(nnew);
+  std::vector<double2> nxy(nnew);
+  std::vector<double> nz(nnew);
+  std::vector<float4> vr(nnew, make_float4(0.f, 0.f, 0.f, 1000.f));
+  for (unsigned q = 0; q < nnew; q++) {
+    const double x = npos[3 * size_t(q)], y = npos[3 * size_t(q) + 1], z = npos[3 * size_t(q) + 2];
+    const double dx = x - C.dom_posmin[0], dy = y - C.dom_posmin[1], dz = z - C.dom_posmin[2];
+    idp[q] = casenp_ + q;  // (inside the domain: checked with the zones, before anything changed)
+    nxy[q] = make_double2(x, y);
+    nz[q] = z;
+    dcell[q] = DcelCell(C.dom_cellcode, unsigned(dx / double(C.scell)), unsigned(dy / double(C.scell)),
+                        unsigned(dz / double(C.scell)));
+  }
+  check_hip(hipMemcpy(cur_.code, code.data(), 2 * size_t(n), hipMemcpyHostToDevice), "upload code");
+  check_hip(hipMemcpy(cur_.idp + n, idp.data(), 4 * size_t(nnew), hipMemcpyHostToDevice), "upload idp");
+  check_hip(hipMemcpy(cur_.code + n, ncode.data(), 2 * size_t(nnew), hipMemcpyHostToDevice), "upload code");
+  check_hip(hipMemcpy(cur_.dcell + n, dcell.data(), 4 * size_t(nnew), hipMemcpyHostToDevice), "upload dcell");
+  check_hip(hipMemcpy(cur_.posxy + n, nxy.data(), 16 * size_t(nnew), hipMemcpyHostToDevice), "upload posxy");
+  check_hip(hipMemcpy(cur_.posz + n, nz.data(), 8 * size_t(nnew), hipMemcpyHostToDevice), "upload posz");
+  check_hip(hipMemcpy(cur_.velrhop + n, vr.data(), 16 * size_t(nnew), hipMemcpyHostToDevice), "upload velrhop");
+  if (cur_.velrhopm1)
+    check_hip(hipMemcpy(cur_.velrhopm1 + n, vr.data(), 16 * size_t(nnew), hipMemcpyHostToDevice), "upload velrhopm1");
+  const unsigned npnew = n + nnew, idmax = casenp_ + nnew - 1u;
+  check_hip(hipMemcpy(&sc_->np, &npnew, 4, hipMemcpyHostToDevice), "set np");
+  check_hip(hipMemcpy(&sc_->io_idmax, &idmax, 4, hipMemcpyHostToDevice), "set IdMax");
+  // -- RunCellDivide and InOutUpdatePartsData of the initial time (:123-133)
+  io_pass_ = 1;
+  try {
+    RunCellDivide();
+  } catch (...) {
+    io_pass_ = 0;
+    throw;
+  }
+  io_pass_ = 0;
+  Sync();
+  CheckErrors();
+}
+
+SphInOutStats SphGpuSingle::InOutStats() {
+  if (!inout_) throw SphError(SPH_ERR_STATE, "the solver has no inlet/outlet zones");
+  Stats();
+  const DevScalars& s = *sc_host_;
+  SphInOutStats r;
+  std::memset(&r, 0, sizeof(r));
+  r.count = s.io_count;
+  r.idmax = s.io_idmax;
+  r.capacity = cap_;
+  r.created = s.io_created;
+  r.removed = s.io_removed;
+  return r;
+}
+
 void SphGpuSingle::Run(unsigned nsteps) {
   check_hip(hipSetDevice(device), "hipSetDevice");
   in_run_ = true;
@@ -2614,6 +2848,9 @@ void SphGpuSingle::CheckErrors() {
   if (s.error_flags & ERR_DT_NAN) throw SphError(SPH_ERR_DT, "The computed Dt is NaN or infinity");
   if (s.error_flags & ERR_PERI_FULL)
     throw SphError(SPH_ERR_NOMEM, "the periodic duplicates of a divide exceed the particle capacity (step " +
+                                      std::to_string(s.nstep) + ")");
+  if (s.error_flags & ERR_INOUT_FULL)
+    throw SphError(SPH_ERR_NOMEM, "the new inlet particles of a step exceed the particle capacity (step " +
                                       std::to_string(s.nstep) + ")");
   if (s.error_flags & ERR_HALO_NODE)
     throw SphError(SPH_ERR_UNSUPPORTED, "slab halo: an mDBC ghost node needs particles beyond the slab's ghost columns");

@@ -19,6 +19,7 @@
 #include "sph_comm.hpp"
 #include "sph_forcing.hpp"
 #include "sph_gauge.hpp"
+#include "sph_inout.hpp"
 #include "sph_kernels.hpp"
 
 namespace sphx {
@@ -156,6 +157,10 @@ class SphGpuSingle {
   // Imposed accelerations and damping zones (sph_forcing.hip), configured once before the first step.
   void SetAccInputs(unsigned n, const SphAccInputDef* defs, unsigned nrows, const double* rows);
   void SetDamping(unsigned n, const SphDampingDef* defs);
+  // Inlet/outlet zones (sph_inout.hip): InOutInit, once before the first step.
+  void SetInOut(const SphInOutDef& def, const SphInOutZoneDef* zones, const double* points, unsigned npoints);
+  SphInOutStats InOutStats();
+  bool InOut() const { return inout_; }
 
   SphConstants C{};
   KConst K{};
@@ -307,6 +312,17 @@ class SphGpuSingle {
   bool peri_ = false, peri_mincap_ = false;
   PeriConst P_{};
   unsigned* periscan_ = nullptr;
+  // inlet/outlet zones (sph_inout.hip): the zone data (host copy and device), the scratch of the
+  // step pass (block counts; the new zone of every particle) and the extrapolation list;
+  // io_pass_ of the divide in flight: 2 the end-of-step one (InOutComputeStep around it), 1 InOutInit's
+  // (the parts-data pass after it only), 0 any other
+  bool inout_ = false;
+  int io_pass_ = 0;
+  InOutDev ioh_{};
+  InOutDev* iodev_ = nullptr;
+  unsigned* ioscan_ = nullptr;
+  unsigned char* ionewiz_ = nullptr;
+  unsigned* iolist_ = nullptr;
   DampZoneDev* dampzones_ = nullptr;  // damping zones in list order (ndamp_ = 0: none, nothing launched)
   int ndamp_ = 0;
   // turns measurement mode: the dt maxima of the next DtVariable are folded at the end of the

@@ -11,6 +11,7 @@
 
 #include "sph_kernels.hpp"
 #include "sph_incdiv.hpp"
+#include "sph_inout.hpp"
 #include "sph_slabpack.hpp"
 
 namespace sphx {
@@ -400,6 +401,64 @@ __global__ __launch_bounds__(256) void k_update_peri(const DevScalars* __restric
   const UpdIn in = upd_load<KIND>(euler, arace, a, shiftpos, p, npb);
   upd_keep(in);
   upd_compute<KIND, true>(sc, K, euler, a, g, shiftpos != nullptr, p, npb, in, &P);
+}
+
+// A case with inlet/outlet zones (its divide is the full sort: no classification rides here).  An
+// inout particle keeps its velocity and density, is displaced by its own velocity (no zone with
+// an interpolated velocity exists here: the reference's vd.x == FLT_MAX branch) and is never
+// marked OUTRHOP (JSphCpu.cpp:1331-1347, 1458-1469, 1555-1571); every other particle is updated
+// as without zones.
+template <int KIND>
+__device__ __forceinline__ void inout_part(const DevScalars* __restrict__ sc, const KConst& K, const PartArrays& a,
+                                           unsigned p, const UpdIn& in) {
+  if (halted(sc)) {  // keep the state, as verlet_part / sym_pre_part / sym_cor_part do
+    if (KIND == UPD_VERLET) a.velrhopm1[p] = in.v1;
+    if (KIND == UPD_SYM_PRE) {
+      a.velrhop[p] = in.v1;
+      a.posxy[p] = in.pxy;
+      a.posz[p] = in.pz;
+    }
+    return;
+  }
+  const double dt = sc->dt;
+  typecode rcode = in.code;
+  if (KIND == UPD_VERLET) {  // the new velocity is velrhop2's, the displacement velrhop1's
+    a.velrhopm1[p] = in.v2;
+    update_pos(K, in.pxy.x, in.pxy.y, in.pz, nc(double(in.v1.x) * dt), nc(double(in.v1.y) * dt),
+               nc(double(in.v1.z) * dt), false, p, a, &rcode);
+  } else if (KIND == UPD_SYM_PRE) {
+    const double dt05 = dt * .5;
+    a.velrhop[p] = in.v1;
+    update_pos(K, in.pxy.x, in.pxy.y, in.pz, nc(double(in.v1.x) * dt05), nc(double(in.v1.y) * dt05),
+               nc(double(in.v1.z) * dt05), false, p, a, &rcode);
+  } else {  // the corrector restarts from the pre-state
+    a.velrhop[p] = in.v2;
+    update_pos(K, in.pxy.x, in.pxy.y, in.pz, nc(double(in.v2.x) * dt), nc(double(in.v2.y) * dt),
+               nc(double(in.v2.z) * dt), false, p, a, &rcode);
+  }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_update_inout(const DevScalars* __restrict__ sc, KConst K, int euler,
+                                                      const float4* __restrict__ arace, PartArrays a, DivGrid g) {
+  const unsigned p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= sc->np) return;
+  const unsigned npb = sc->npb;
+  const UpdIn in = upd_load<KIND>(euler, arace, a, nullptr, p, npb);
+  upd_keep(in);
+  if (p >= npb && CodeIsFluidInout(in.code)) inout_part<KIND>(sc, K, a, p, in);
+  else upd_compute<KIND>(sc, K, euler, a, g, false, p, npb, in);
+}
+
+void launch_update_inout(hipStream_t stm, unsigned cap, DevScalars* sc, const KConst& K, int kind, bool euler,
+                         const float4* arace, PartArrays a, DivGrid g) {
+  const unsigned nb = (cap + 255) / 256;
+  if (kind == UPD_VERLET)
+    hipLaunchKernelGGL(k_update_inout<UPD_VERLET>, dim3(nb), dim3(256), 0, stm, sc, K, int(euler), arace, a, g);
+  else if (kind == UPD_SYM_PRE)
+    hipLaunchKernelGGL(k_update_inout<UPD_SYM_PRE>, dim3(nb), dim3(256), 0, stm, sc, K, 0, arace, a, g);
+  else
+    hipLaunchKernelGGL(k_update_inout<UPD_SYM_COR>, dim3(nb), dim3(256), 0, stm, sc, K, 0, arace, a, g);
 }
 
 // The update with the incremental divide's classification of the same particles (sph_incdiv.hpp):

@@ -5,7 +5,8 @@ Mirrors what ``JSph`` reads before the first step, restricted to what the hot pa
 this core runs (fixed and moving DBC/mDBC boundaries, floating bodies with RigidAlgorithm 0, 1 or 2
 and the materials of ``<properties>``, fluid,
 Wendland, artificial viscosity, DDT 0-3,
-Verlet / Symplectic, periodic boundaries); anything else raises ``CaseError`` the way the
+Verlet / Symplectic, periodic boundaries, the inlet/outlet zones of ``<special><inout>``:
+``inout.py``); anything else raises ``CaseError`` the way the
 reference refuses an invalid configuration, never silently ignored:
 
 * constants  — ``JCaseCtes::ReadXmlRun`` (JCaseCtes.cpp:201-215) via
@@ -533,6 +534,8 @@ class XmlCase:
                     if self.rheology == 2 and _active(ch):
                         raise CaseError(f"<special><{ch.tag}> with NN multiphase is not supported by this core.")
                     continue  # read below, once the blocks are known
+                if ch.tag == "inout":
+                    continue  # read last, once the particles and the map limits are known (inout.py)
                 raise CaseError(f"<special><{ch.tag}> is not supported by this core.")
         self._load_blocks(_node(ex, "particles"))
         # <special><accinputs> / <damping> (JSph::LoadCaseConfig: JDsAccInput, JDsDamping)
@@ -590,6 +593,20 @@ class XmlCase:
                 (bool(self.gauges), "<special><gauges>")) if on]
             if bad:
                 raise CaseError(f"{', '.join(bad)} with periodic boundaries: not supported by this core.")
+        # what this core runs with <special><inout>: DBC, artificial viscosity, one phase, fixed
+        # boundaries only, no periodic axes, Symmetry or gauges, from the case's start
+        inode = sp.find("inout") if sp is not None else None
+        if inode is not None and _active(inode):
+            bad = [what for on, what in (
+                (self.tvisco != 1, "Laminar+SPS viscosity"), (self.shift_mode != 0, "Shifting"),
+                (self.tboundary == 2, "mDBC"), (bool(self.case_nfloat), "Floating bodies"),
+                (bool(self.case_nmoving), "Moving boundaries"), (bool(self.peri_active), "Periodic boundaries"),
+                (self.symmetry, "Symmetry"), (self.rheology == 2, "NN multiphase"),
+                (bool(self.gauges), "<special><gauges>")) if on]
+            if bad:
+                raise CaseError(f"{', '.join(bad)} with <special><inout>: not supported by this core.")
+            if partbegin:  # JSphCpuSingle_InOut.cpp:76
+                raise CaseError("Simulation restart not allowed when Inlet/Outlet is used.")
         # -- particles (JPartsLoad4::LoadParticles) ------------------------------------
         self.partbegin = int(partbegin)
         self.partbegin_dir = None
@@ -648,6 +665,16 @@ class XmlCase:
         self._boundnormal = None
         if self.tboundary == 2:
             self._boundnormal = self._load_normals()
+        # <special><inout> (JSph.cpp:1143-1148; JSphCpuSingle::InOutInit): the zones and the initial
+        # inout particles, which the solver appends (XmlCase.np stays the case's count)
+        self.inout = None
+        if inode is not None and _active(inode):
+            from .inout import load_inout
+
+            self.messages = getattr(self, "messages", [])
+            self.inout = load_inout(inode, self, self.messages)
+            # CodeNewFluid (JSphMk.cpp:121): the fluid code after the case's fluid blocks
+            self.inout["codenewpart"] = CODE_TYPE_FLUID | sum(1 for b in self.blocks if b["type"] == "fluid")
 
     # -- JSphCpu::InitFloating (JSphCpu.cpp:1885-1905) ---------------------------------------
     def _restart_floatings(self) -> None:

@@ -64,6 +64,9 @@
  *   SphCaseDef.peri_active ..... periodic boundaries: JSphCpuSingle::RunPeriodic before every
  *                                divide (JSphCpuSingle.cpp:361-431), the wrap of JSphCpu::UpdatePos
  *                                (JSphCpu.cpp:1254-1291); single domain, DBC, no bodies
+ *   sph_solver_set_inout ....... inlet/outlet zones: JSphCpuSingle::InOutInit, then InOutComputeStep
+ *     sph_solver_inout_stats     in place of every end-of-step divide (JSphCpuSingle_InOut.cpp:72-255,
+ *                                JSphInOut.cpp, JSphCpu_InOut.cpp); single domain, DBC, no bodies
  */
 #ifndef SPHCORE_H
 #define SPHCORE_H
@@ -805,6 +808,69 @@ typedef struct SphDampingDerived {
 } SphDampingDerived;
 int sph_accinput_velocities(uint32_t nrows, const double* rows, double* out);
 int sph_damping_derive(const SphDampingDef* def, uint32_t index, SphDampingDerived* out);
+
+/* ---- inlet/outlet zones (<special><inout>, JSphInOut*): buffer zones of `layers` layers of
+ * particles behind a plane that feed fluid into the domain and take it out.  The values are
+ * what JSphInOut::Config holds after loading the XML (the planes, widths, config bytes, velocity
+ * coefficients, box limits and free limits; XmlCase.inout computes them).
+ * sph_solver_set_inout is JSphCpuSingle::InOutInit (JSphCpuSingle_InOut.cpp:72-137): the
+ * initial inout particles (every zone's points, `layers` times, one dp apart against its
+ * direction; ids from CaseNp; code 0x1fe0 + zone; velocity 0, density 1000) are appended, the
+ * fluid within 0.8 dp of one is dropped (InitCheckProximity; a boundary or inout particle that
+ * close is SPH_ERR_ARG), the divide runs and the zones' velocity and density are imposed.
+ * After every step, in place of the plain divide, InOutComputeStep (:146-223): fluid entering a
+ * zone is removed or converted, an inout particle that crosses the plane becomes fluid and is
+ * replaced one width behind, one that leaves the zone is dropped; after the divide the imposed
+ * velocity and density: a constant or hydrostatic density, a uniform, linear or parabolic
+ * velocity, or either one extrapolated from the fluid at the particle's ghost node (its mirror
+ * image in the plane), first order when |det A| >= determlimit, else zeroth order.
+ * The particle capacity is fixed here: the particles held + resize_plus0 (NpResizePlus0:
+ * memoryresize size0 x points x layers), or `capacity` when not 0.  A step whose new particles
+ * do not fit creates none, sets SPH_FLAG_INOUT_FULL and stops the run on the device
+ * (SPH_ERR_NOMEM at the next status read; the state stays downloadable).
+ * Single domain, DBC, artificial viscosity, Wendland kernel, no moving or floating bodies, no
+ * periodic axes, Symmetry, NN phases or gauges: SPH_ERR_UNSUPPORTED otherwise, as to
+ * sph_solver_set_time and the phase-level calls (sph_divide, sph_compute_dt, sph_step_*,
+ * sph_interaction_forces) of a solver with zones: only sph_solver_run steps it.
+ * SPH_ERR_STATE after a step. */
+#define SPH_MAX_INOUTZONES 16
+/* error_flags bit: the new inlet particles of a step exceeded the particle capacity (fatal) */
+#define SPH_FLAG_INOUT_FULL 256u
+typedef struct SphInOutZoneDef {
+  double direction[3];          /* Direction (unit vector into the domain)          */
+  float plane[4];               /* Plane (a, b, c, d)                               */
+  float veldata[2][4];          /* VelData[2 i], VelData[2 i + 1]                   */
+  float boxlimitmin[3], boxlimitmax[3];
+  float width;                  /* float(dp layers)                                 */
+  float zsurf;                  /* Zsurf (FLT_MAX: undefined)                       */
+  uint32_t cfgzone, cfgupdate;  /* GetConfigZone / GetConfigUpdate bytes            */
+  uint32_t layers;
+  uint32_t point0, npoints;     /* its initially valid points in `points`           */
+  uint32_t pad;
+} SphInOutZoneDef;
+typedef struct SphInOutDef {
+  uint32_t nzones;              /* <= SPH_MAX_INOUTZONES                            */
+  int32_t useboxlimit;
+  int32_t extrapolatemode;      /* 1 fast-single, 2 single, 3 double                */
+  uint32_t codenewpart;         /* CodeNewFluid (JSphMk.cpp:121)                    */
+  float determlimit;
+  float freelimitmin[3], freelimitmax[3];
+  uint32_t resize_plus0;        /* NpResizePlus0                                    */
+  uint32_t capacity;            /* 0, or the particle capacity                      */
+  uint32_t pad;
+} SphInOutDef;
+typedef struct SphInOutStats {
+  uint32_t count;               /* inout particles now                              */
+  uint32_t idmax;               /* IdMax                                            */
+  uint32_t capacity;            /* particle capacity                                */
+  uint32_t pad;
+  uint64_t created;             /* created by the zones since sph_solver_set_inout  */
+  uint64_t removed;             /* dropped or removed by the zones' rules           */
+} SphInOutStats;
+/* points[npoints][3]: the initially valid points of every zone (zone i: point0, npoints). */
+int sph_solver_set_inout(SphSolver* s, const SphInOutDef* def, const SphInOutZoneDef* zones, const double* points,
+                         uint32_t npoints);
+int sph_solver_inout_stats(SphSolver* s, SphInOutStats* out);
 
 #ifdef __cplusplus
 }
