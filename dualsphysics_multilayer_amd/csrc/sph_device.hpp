@@ -65,6 +65,7 @@ struct KConst {
   float awen;  // Wendland W normalisation (mDBC)
   int mdbc;    // TBoundary == BC_MDBC: DDT (Molteni) keeps bound neighbours (JSphCpu.cpp:730)
   int scelldiv;  // 1 CellMode=full (cells of 2h), 2 half (cells of h): neighbour rows +-scelldiv
+  int tilefull;  // SPH_TILE_FULL test hook: full 32-record test groups, drain rounds of 128 (sph_tiled.hpp)
   // v5.0 NN multiphase (sph_nn.hip) and shifting (JSphShifting::RunCpu, JSphShifting.cpp:388-418)
   int nn;          // RheologyTreatment == 2
   int nntvisco;    // TpVisco of the NN interaction: 1 artificial, 2 laminar, 3 constitutive eq.

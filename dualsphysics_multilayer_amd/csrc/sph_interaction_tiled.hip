@@ -276,6 +276,18 @@ __device__ __forceinline__ void drain_words(const KConst& K, const P1& p, unsign
                                             const typename CRecT<FT>::type* __restrict__ sC, const PassK& Q,
                                             TAcc& a);
 
+// Which instantiations stop a window's last test group at the window's end (the block loop of
+// test32, sph_tiled.hpp): Wendland with DDT 0, 2 or 3, without FTMODE_Ext.  The others sit at
+// or just under the 4-wave register budget, where the loop's extra live values cost more
+// than the skipped tests save: DDT1 under the budget ran cfg3 at 5.35-5.38 ms against
+// 5.25, the half-cell Cubic forms went from <= 128 to 129-131 VGPRs (3 waves per SIMD) and
+// the FTMODE_Ext forms from 129-135 to 129-141.  They keep the full groups, compiled as
+// before.
+template <int TDENSITY>
+constexpr bool tiled_blocks() {
+  return (TDENSITY & 7) != 1 && (TDENSITY & (16 | 32)) == 0;
+}
+
 // One drain unit: the lane's candidates in up to two staged windows [wa0,wa1) and
 // [wb0,wb1) (two point-mirrored neighbour rows, or one row), all positions relative to
 // the item, drained as ONE set.  How many real neighbours a particle has in one row
@@ -300,12 +312,13 @@ __device__ __forceinline__ void tile_unit(const KConst& K, const P1& p, float th
                                           const typename CRecT<FT>::type* __restrict__ sC, const PassK& Q, TAcc& a,
                                           int self = -1) {
   const float px2 = -2.f * p.x, py2 = -2.f * p.y, pz2 = -2.f * p.z;
+  constexpr bool BLK = tiled_blocks<TDENSITY>();
   for (int off = 0;; off += 128) {  // a second round only for windows of > 128 candidates
     const int na = wa1 - wa0 - off, nb = wb1 - wb0 - off;
     if (na <= 0 && nb <= 0) break;
     unsigned long long c0, c1, c2, c3;
-    test128(sA, wa0 + off, min(na, 128), px2, py2, pz2, thr, c0, c1);
-    test128(sA, wb0 + off, min(nb, 128), px2, py2, pz2, thr, c2, c3);
+    test128<BLK>(sA, wa0 + off, min(na, 128), px2, py2, pz2, thr, c0, c1, K.tilefull != 0);
+    test128<BLK>(sA, wb0 + off, min(nb, 128), px2, py2, pz2, thr, c2, c3, K.tilefull != 0);
     if (SELF) {
       const int k = self - (wa0 + off);
       if (k >= 0 && k < 64) c0 &= ~(1ull << k);
@@ -324,13 +337,14 @@ __device__ __forceinline__ void tile_unit4(const KConst& K, const P1& p, float t
                                            const typename CRecT<FT>::type* __restrict__ sC, const PassK& Q,
                                            TAcc& a) {
   const float px2 = -2.f * p.x, py2 = -2.f * p.y, pz2 = -2.f * p.z;
+  constexpr bool BLK = tiled_blocks<TDENSITY>();
   for (int off = 0;; off += 64) {  // a second round only for windows of > 64 candidates
     const int n0 = w1.x - w0.x - off, n1 = w1.y - w0.y - off, n2 = w1.z - w0.z - off, n3 = w1.w - w0.w - off;
     if (n0 <= 0 && n1 <= 0 && n2 <= 0 && n3 <= 0) break;
-    const unsigned long long c0 = test64(sA, w0.x + off, min(n0, 64), px2, py2, pz2, thr);
-    const unsigned long long c1 = test64(sA, w0.y + off, min(n1, 64), px2, py2, pz2, thr);
-    const unsigned long long c2 = test64(sA, w0.z + off, min(n2, 64), px2, py2, pz2, thr);
-    const unsigned long long c3 = test64(sA, w0.w + off, min(n3, 64), px2, py2, pz2, thr);
+    const unsigned long long c0 = test64<BLK>(sA, w0.x + off, min(n0, 64), px2, py2, pz2, thr, K.tilefull != 0);
+    const unsigned long long c1 = test64<BLK>(sA, w0.y + off, min(n1, 64), px2, py2, pz2, thr, K.tilefull != 0);
+    const unsigned long long c2 = test64<BLK>(sA, w0.z + off, min(n2, 64), px2, py2, pz2, thr, K.tilefull != 0);
+    const unsigned long long c3 = test64<BLK>(sA, w0.w + off, min(n3, 64), px2, py2, pz2, thr, K.tilefull != 0);
     drain_words<TDENSITY, MODE, FT>(K, p, c0, c1, c2, c3, w0.x + off, w0.y + off, w0.z + off, w0.w + off, sA, sB,
                                     sC, Q, a);
   }

@@ -292,7 +292,15 @@ static KConst make_kconst(const SphConstants& c) {
   K.awen = c.awen;
   K.mdbc = (c.tboundary == SPH_BOUND_MDBC) ? 1 : 0;
   K.scelldiv = c.scelldiv;
-  K.nn = (c.rheology == SPH_RHEOLOGY_NN) ? 1 : 0;
+  {  // SPH_TILE_FULL=1 (test hook, read once): the tiled kernels' full test groups and rounds of 128
+    static const bool full = [] {
+      const char* e = std::getenv("SPH_TILE_FULL");
+      return e && std::atoi(e) != 0;
+    }();
+    if (full) test_hook_notice("SPH_TILE_FULL");
+    K.tilefull = full ? 1 : 0;
+  }
+  K.nn =(c.rheology == SPH_RHEOLOGY_NN) ? 1 : 0;
   K.nntvisco = c.tvisco;
   K.nnvelgrad = c.velgrad;
   K.tvisco = c.tvisco;

@@ -20,8 +20,8 @@ constexpr int TB = 128;        // threads per block = max p1 per item (2 waves)
 // mirrored row pair fits one segment for 94% of the units instead of 81%); 0.936 at 580
 // (7 blocks/CU), 1.02 at 672 (6 blocks/CU).  The position records (sA) are followed by
 // the velrhop records (sB) in ONE LDS array in every tiled kernel, so the candidate
-// test's last group of 32 (up to 31 records past a window ending at the capacity) reads
-// inside that array; its bits are masked off.
+// test's last group (it may read up to 31 records past a window ending at the capacity,
+// see test_groups) reads inside that array; its bits are masked off.
 constexpr int TCAP = SPH_TCAP;
 // With floating bodies a record is 48 B (the third part a float4): 416 records keep the
 // block at <= 20 KB of LDS, i.e. the same 8 blocks (4 waves/SIMD) per CU.
@@ -61,10 +61,22 @@ constexpr unsigned ITEM_BOUND = 0x80000000u;  // flag in item.x: p1 are boundary
 // compare per candidate on one ds_read_b128) against a threshold inflated by 1e-4 (the
 // expanded form rounds to ~1e-6 relative); the body recomputes |p-A|^2 exactly and applies
 // the reference's test, so no pair is lost or added.
-// 32 candidates b[0..31] -> bits (bit k = candidate k): the compare lands in VCC and
-// v_addc_co_u32 shifts it in (bits = 2 bits + vcc), two VALU per candidate besides the 3
-// FMAs instead of compare + select + or.  Candidates in descending order so candidate k
-// ends at bit k.  (VCC only: no memory access.)
+// 8 candidates b[0..7] shifted into bits (bit k = candidate k of the block, the earlier
+// bits move up by 8): the compare lands in VCC and v_addc_co_u32 shifts it in (bits =
+// 2 bits + vcc), two VALU per candidate besides the 3 FMAs instead of compare + select +
+// or.  Candidates in descending order so candidate k ends at bit k.  (VCC only: no memory
+// access.)
+__device__ __forceinline__ void test8(const float4* __restrict__ b, float px2, float py2, float pz2, float thr,
+                                      unsigned& bits) {
+#pragma unroll
+  for (int ji = 7; ji >= 0; ji--) {
+    const float4 A = b[ji];
+    const float q = fmaf(px2, A.x, fmaf(py2, A.y, fmaf(pz2, A.z, A.w)));
+    asm("v_cmp_ge_f32_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc" : "+v"(bits) : "v"(thr), "v"(q) : "vcc");
+  }
+}
+
+// 32 candidates b[0..31] -> bits (bit k = candidate k), in the same way.
 __device__ __forceinline__ unsigned test32(const float4* __restrict__ b, float px2, float py2, float pz2,
                                            float thr) {
   unsigned bits = 0u;
@@ -77,36 +89,80 @@ __device__ __forceinline__ unsigned test32(const float4* __restrict__ b, float p
   return bits;
 }
 
-// One window of n (<= 32 * NG) staged records from sA + s0 in groups of 32 -> words w[NG]
-// (a group past the window's end reads up to 31 records beyond it, inside the staging
-// array, and its bits are masked off).  n <= 0 gives empty words.
-template <int NG>
-__device__ __forceinline__ void test_groups(const float4* __restrict__ sA, int s0, int n, float px2, float py2,
-                                            float pz2, float thr, unsigned (&w)[NG]) {
+// Test hook SPH_TILE_FULL=1 (read once by the host, passed as KConst::tilefull): every
+// group tests its 32 records whatever the windows' lengths.  Results are the same bit for
+// bit either way.
+//
+// One group of up to 32 candidates b[0..31] -> bits (bit k = candidate k), `left` of them
+// inside the lane's window.  The group is tested in blocks of 8 records, in descending
+// order, and only from the block that the longest window of the wave's lanes reaches
+// (wave-uniform: a ballot per block, no reduction): a 99-record window's last group costs
+// 8 tests, not 32.  A loop over the blocks, not unrolled: four unrolled blocks, each
+// skipped by a uniform branch, gave the headline kernel 110 VGPRs instead of 127, but
+// four times the test code at each of the ~100 inlined call sites of a kernel: the
+// library grew from 17 to 32 MB and its build from 5 to 19 minutes.  A
+// skipped block leaves its bits 0; bits at and beyond `left` are masked off by the caller.
+__device__ __forceinline__ unsigned test32_blocks(const float4* __restrict__ b, int left, bool full, float px2,
+                                                  float py2, float pz2, float thr) {
+  unsigned bits = 0u;
+  const int top = full                             ? 3
+                  : __ballot(left > 24) != 0ull ? 3
+                  : __ballot(left > 16) != 0ull ? 2
+                  : __ballot(left > 8) != 0ull  ? 1
+                                                   : 0;
+#pragma unroll 1
+  for (int blk = top; blk >= 0; blk--) test8(b + 8 * blk, px2, py2, pz2, thr, bits);
+  return bits;
+}
+
+// One window of n (<= 32 * NG) staged records from sA + s0 in groups of 32 -> words w[NG].
+// n <= 0 gives empty words.
+// BLK false: every group of a lane's window tests 32 records (a group past the window's
+// end reads up to 31 records beyond it, inside the staging array, and its bits are masked
+// off).
+// BLK true (the kernels of tiled_blocks(), sph_interaction_tiled.hip): control flow is
+// wave-uniform.  A group runs while any lane of the wave has records left in it, and a lane
+// that has none reads the records at sA instead (its word stays 0), so no lane reads
+// further past its window than with BLK false.  A window's last group stops at the
+// 8-record block that holds the end of the longest window among the wave's lanes, so a
+// lane reads up to 7 records past that window (up to 31 past its own, and with `full`
+// always 31), inside the staging array; the bits beyond its own window are masked off.
+template <int NG, bool BLK>
+__device__ __forceinline__ void test_groups(const float4* __restrict__ sA, int s0, int n, bool full, float px2,
+                                            float py2, float pz2, float thr, unsigned (&w)[NG]) {
   const float4* __restrict__ b = sA + s0;
 #pragma unroll
   for (int g = 0; g < NG; g++) w[g] = 0u;
 #pragma unroll
   for (int g = 0; g < NG; g++) {
     const int left = n - g * 32;
-    if (left <= 0) break;
-    w[g] = test32(b + g * 32, px2, py2, pz2, thr) & (left >= 32 ? ~0u : ((1u << left) - 1u));
+    if constexpr (BLK) {
+      if (__ballot(left > 0) == 0ull) break;
+      const unsigned m = left >= 32 ? ~0u : left <= 0 ? 0u : ((1u << left) - 1u);
+      w[g] = test32_blocks(left > 0 ? b + g * 32 : sA, left, full, px2, py2, pz2, thr) & m;
+    } else {
+      if (left <= 0) break;
+      w[g] = test32(b + g * 32, px2, py2, pz2, thr) & (left >= 32 ? ~0u : ((1u << left) - 1u));
+    }
   }
 }
 
 // A window of <= 64 candidates -> one 64-bit mask (the short 5-cell windows of CellMode=half).
+template <bool BLK = false>
 __device__ __forceinline__ unsigned long long test64(const float4* __restrict__ sA, int s0, int n, float px2,
-                                                     float py2, float pz2, float thr) {
+                                                     float py2, float pz2, float thr, bool full = false) {
   unsigned w[2];
-  test_groups<2>(sA, s0, n, px2, py2, pz2, thr, w);
+  test_groups<2, BLK>(sA, s0, n, full, px2, py2, pz2, thr, w);
   return (static_cast<unsigned long long>(w[1]) << 32) | w[0];
 }
 
 // A window of <= 128 candidates -> two 64-bit masks.
+template <bool BLK = false>
 __device__ __forceinline__ void test128(const float4* __restrict__ sA, int s0, int n, float px2, float py2,
-                                        float pz2, float thr, unsigned long long& m0, unsigned long long& m1) {
+                                        float pz2, float thr, unsigned long long& m0, unsigned long long& m1,
+                                        bool full = false) {
   unsigned w[4];
-  test_groups<4>(sA, s0, n, px2, py2, pz2, thr, w);
+  test_groups<4, BLK>(sA, s0, n, full, px2, py2, pz2, thr, w);
   m0 = (static_cast<unsigned long long>(w[1]) << 32) | w[0];
   m1 = (static_cast<unsigned long long>(w[3]) << 32) | w[2];
 }
