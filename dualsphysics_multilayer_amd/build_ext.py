@@ -21,7 +21,8 @@ CSRC = os.path.join(HERE, "csrc")
 OUTDIR = os.path.join(HERE, "lib")
 LIBNAME = "libsphcore.so"
 SOURCES = ["sph_divide.hip", "sph_interaction.hip", "sph_interaction_tiled.hip", "sph_nn.hip", "sph_ext.hip", "sph_step.hip", "sph_slab.hip", "sph_mdbc.hip", "sph_bodies.hip",
-           "sph_gauge.hip", "sph_forcing.hip", "sph_periodic.hip", "sph_dem.hip", "sph_inout.hip", "sph_solver.cpp", "sph_comm.cpp", "sph_bi4.cpp", "sph_capi.cpp"]
+           "sph_gauge.hip", "sph_forcing.hip", "sph_periodic.hip", "sph_dem.hip", "sph_inout.hip", "sph_constants.cpp", "sph_solver.cpp", "sph_solver_slab.cpp",
+           "sph_solver_bodies.cpp", "sph_solver_gauges.cpp", "sph_solver_forcing.cpp", "sph_solver_inout.cpp", "sph_comm.cpp", "sph_bi4.cpp", "sph_capi.cpp"]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 LDFLAGS = ["-L" + os.path.join(ROCM, "lib"), "-lrccl", "-Wl,-rpath," + os.path.join(ROCM, "lib"), "-pthread"]
 ARCH = os.environ.get("SPH_OFFLOAD_ARCH", "gfx950")

@@ -42,7 +42,6 @@ class RcclTransport final : public SlabTransport {
   }
   ~RcclTransport() override {
     if (comm_) (aborted_ ? ncclCommAbort(comm_) : ncclCommDestroy(comm_));
-    if (gather_) (void)hipFree(gather_);
   }
   void group_begin() override { check_nccl(ncclGroupStart(), "ncclGroupStart"); }
   void group_end() override { check_nccl(ncclGroupEnd(), "ncclGroupEnd"); }
@@ -82,21 +81,18 @@ class RcclTransport final : public SlabTransport {
   // as LocalTransport's host sum (ncclAllReduce's reduction order is the library's).
   void allreduce_sum_f32(float* d, int n, hipStream_t s) override {
     const size_t need = size_t(n) * size_t(nranks);
-    if (need > gathercap_) {
+    if (need > gather_.cap()) {
       check_hip(hipStreamSynchronize(s), "allreduce: sync");
-      if (gather_) check_hip(hipFree(gather_), "hipFree");
-      gathercap_ = need;
-      check_hip(hipMalloc((void**)&gather_, sizeof(float) * gathercap_), "hipMalloc allreduce scratch");
+      gather_.reserve(need, 0, true);
     }
-    check_nccl(ncclAllGather(d, gather_, size_t(n), ncclFloat, comm_, s), "ncclAllGather");
-    launch_rank_ordered_sum(s, gather_, n, nranks, d);
+    check_nccl(ncclAllGather(d, gather_.ptr(), size_t(n), ncclFloat, comm_, s), "ncclAllGather");
+    launch_rank_ordered_sum(s, gather_.ptr(), n, nranks, d);
   }
 
  private:
   ncclComm_t comm_ = nullptr;
   bool aborted_ = false;
-  float* gather_ = nullptr;
-  size_t gathercap_ = 0;
+  GrowBuf<float> gather_;
 };
 
 std::unique_ptr<SlabTransport> make_rccl_transport(const unsigned char id[128], int rank, int nranks) {

@@ -17,6 +17,7 @@
 
 #include "../../include/sphcore.h"
 #include "sph_comm.hpp"
+#include "sph_devmem.hpp"
 #include "sph_forcing.hpp"
 #include "sph_gauge.hpp"
 #include "sph_inout.hpp"
@@ -33,7 +34,7 @@ void check_hip(hipError_t e, const char* what);
 void test_hook_notice(const char* name);
 void derive_constants(const SphCaseDef& c, SphConstants& k);
 // Imposed accelerations / damping zones: the integrated velocity rows [nrows][6] of an input's
-// rows [nrows][7], and the derived geometry of zone i of a list (sph_solver.cpp; no device).
+// rows [nrows][7], and the derived geometry of zone i of a list (sph_solver_forcing.cpp; no device).
 void accinput_velocities(unsigned nrows, const double* rows, double* out);
 void derive_damping(const SphDampingDef& d, unsigned i, DampZoneDev& z);
 // Ghost columns per slab face (scelldiv, +1 with mDBC).
@@ -207,8 +208,7 @@ class SphGpuSingle {
   bool mdbc_corrector_ = false;   // MDBCCorrector: mDBC before the Symplectic corrector too
   unsigned* mdbclist_ = nullptr;  // mDBC: wet boundary particles of this interaction [npb] + count
   void* mdbcsums_ = nullptr;      // mDBC: reduced sums per listed particle (pass 2 -> solve)
-  MdbcFaceRec* mdbcface_ = nullptr;  // slabs + mDBC: send left, send right, recv left, recv right (face sizes + 1)
-  unsigned long long mdbcfacecap_ = 0;
+  GrowBuf<MdbcFaceRec> mdbcface_;  // slabs + mDBC: send left, send right, recv left, recv right (face sizes + 1)
   // SPH_SLAB_MINCAP test hook: every slab buffer starts at (or grows to) its minimum, so each
   // grow-and-redo path runs (tests/test_gpu_slab.py checks the runs stay bitwise the same)
   bool slab_mincap_ = false;
@@ -234,12 +234,16 @@ class SphGpuSingle {
   float4* tau_ = nullptr;
   // slabs: face records of eta / tau for the neighbours' ghosts; sizes (records) of the
   // send-left, send-right, receive-left, receive-right regions, known to both sides of a face
-  NNFaceRec* nnface_ = nullptr;
-  unsigned long long nnfacecap_ = 0;
+  GrowBuf<NNFaceRec> nnface_;
   unsigned face_sl_ = 0, face_sr_ = 0, face_rl_ = 0, face_rr_ = 0;
   unsigned* idxmap_ = nullptr;  // idp -> local index [CaseNp]
   unsigned casenp_ = 0;
   void NNFaceExchange();
+  void MdbcFaceExchange();
+  // The face re-send of both: `pack` fills the send-left / send-right regions of `buf`,
+  // `apply` reads the receive-left / receive-right regions (sph_solver_slab.cpp)
+  template <class Rec, class Pack, class Apply>
+  void FaceExchange(GrowBuf<Rec>& buf, Pack pack, Apply apply);
   unsigned* begincell_ = nullptr;
   uint4* items_ = nullptr;        // tiled-interaction work items (per divide)
   unsigned* rowtmp_ = nullptr;    // per-row item counts/offsets
@@ -330,8 +334,8 @@ class SphGpuSingle {
   // GPU as on a rank's own; folded_ready_: DtVariable finds them folded
   int fold_turn_ = -1;
   bool folded_ready_ = false;
-  std::vector<void*> allocs_;   // fixed-size allocations
-  std::vector<void*> pallocs_;  // capacity-sized (per-particle) allocations
+  DevArena allocs_;   // fixed-size allocations
+  DevArena pallocs_;  // capacity-sized (per-particle) allocations
   // slab decomposition
   std::unique_ptr<SlabTransport> transport_;
   SlabConfig slabcfg_;
@@ -348,11 +352,15 @@ class SphGpuSingle {
   SlabCounts* slabcnt_host_ = nullptr;
   unsigned* packtiles_ = nullptr;
   SlabSendBufs send_{nullptr, nullptr, nullptr, nullptr, 0, 0};
-  SlabGhost* recvg_ = nullptr;
-  SlabRec* recvm_ = nullptr;
-  unsigned long long recvgcap_ = 0, recvmcap_ = 0;
-  void* sendgbuf_ = nullptr;
-  void* sendmbuf_ = nullptr;
+  GrowBuf<SlabGhost> recvg_;
+  GrowBuf<SlabRec> recvm_;
+  // the send buffers behind send_, counted in records per face (an element has the size of
+  // two records): send_.gl's gcap records, then send_.gr's; the migrants' alike
+  template <class T>
+  struct PerFace { T rec[2]; };
+  GrowBuf<PerFace<SlabGhost>> sendg_;
+  GrowBuf<PerFace<SlabRec>> sendm_;
+  void BindSendBufs();  // send_'s pointers and capacities from sendg_ / sendm_
   // the ghost exchange after the divide (sph_kernels.hpp SlabFaces)
   SlabFaces faces_{};
   unsigned long long xg_sl_ = 0, xg_sr_ = 0, xg_rl_ = 0, xg_rr_ = 0;  // ghost records of this exchange

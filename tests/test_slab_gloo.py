@@ -268,7 +268,7 @@ def _bodies_worker(rank, world, port):
     isb = np.arange(case.np) < case.npb
     left = rank - 1 if rank > 0 else None
     right = rank + 1 if rank + 1 < world else None
-    W = int(k["scelldiv"]) + 1  # ghost columns per face with mDBC (sph_solver.cpp ghost_width)
+    W = int(k["scelldiv"]) + 1  # ghost columns per face with mDBC (sph_constants.cpp ghost_width)
     send_l = case.idp[isb & owned & (col < c0 + W)] if left is not None else np.zeros(0, np.uint32)
     send_r = case.idp[isb & owned & (col >= c1 - W)] if right is not None else np.zeros(0, np.uint32)
     got_from_left = _sendrecv_arrays([send_r], right, left, [np.uint32])
